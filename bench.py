@@ -11,12 +11,20 @@ i % rebuild_every == 0.  `value` = steps / wall time of the timed region, inputs
 resident in HBM; the label reports how many builds the timed region contained.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong|config4]
+                    [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no launcher in the environment, bench.py starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD
 process (before anything touches the GPU) and relays its JSON line and exit code.
 
-Extra keys on the same JSON line (one GPU):
+A plain run sets up, warms up, times the K steps and prints the headline line
+(`ms_per_step` = wall time of the timed region / K).  --dump-outputs DIR then
+writes the last timed step's MVM output, the rows a caller receives, to
+DIR/out.npy (float32, [rows, vd]; above DUMP_MAX_BYTES a fixed seeded sample of
+rows, whose indices go to DIR/out_rows.npy as float64).  The inputs are seeded:
+the same arguments give the same inputs on every run.
+
+Extra keys on the same JSON line, only with --full (one GPU):
   warm_mvms_per_s / cold_mvms_per_s   apply only / build + apply per call (what the
                    reference does on every call, permutohedral.h:272)
   roofline         dominant stage of the timed region: algorithmic bytes
@@ -41,7 +49,7 @@ rate of one operator, MVMs/s -- never scaled by the problem size:
   --scaling strong  (default) N=1e6 TOTAL, BASELINE.json's metric as written
   --scaling config4 N=4e6 TOTAL (BASELINE.json configs[3])
   --scaling weak    1e6 points PER GPU: the operator grows with the rank count
-Whatever the mode, a multi-GPU line also carries the other legs (`strong`, `config4`
+Whatever the mode, a multi-GPU line with --full also carries the other legs (`strong`, `config4`
 with vd 1 and 11, `weak_1e6_per_gpu`, `weak_4e6_per_gpu`), each with per-stage us per
 rank and `exchange: {kind, bytes, us}`, so that one 1/2/4/8 sweep yields every curve;
 `columns_mode` (every rank applies the whole operator to its own right-hand-side column:
@@ -91,7 +99,16 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL) for real runs; gloo to rehearse ranks on one GPU")
     ap.add_argument("--skip-weak4", dest="no_weak4", action="store_true", help="multi-rank runs: skip the 4e6-points-per-GPU weak-scaling leg")
     ap.add_argument("--dump", default=None, help="write every rank's output rows of one MVM to <DUMP>.rank<r>.npz (checked by tests/check_bench_dump.py)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (warm / cold rates, roofline, fine regime, configs 3-5, "
+                         "CPU baseline; multi-rank: exchange records and the other scaling curves); the --skip-* "
+                         "switches act on these legs")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args):
@@ -139,6 +156,30 @@ def synth(n, d, vd, seed=1234, lo=0, hi=None):
         xs.append(x[a:z])
         vs.append(v[a:z])
     return torch.cat(xs, 0), torch.cat(vs, 0)
+
+
+DUMP_MAX_BYTES = 32_000_000     # --dump-outputs: a larger output is sampled by rows (the files stay under 64 MB in all)
+
+
+def dump_outputs(ctx, job, path):
+    """--dump-outputs: job.out (the MVM of the last timed step) over all ranks, in row order, to path/out.npy.  An output
+    above DUMP_MAX_BYTES is replaced by a fixed seeded sample of its rows, their indices in path/out_rows.npy."""
+    n, vd = job.n_total, job.vd
+    rows = None
+    if n * vd * 4 > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=DUMP_MAX_BYTES // (4 * vd + 8), replace=False))
+    local = job.out.cpu().numpy()
+    if rows is not None:
+        local = local[rows[(rows >= job.lo) & (rows < job.hi)] - job.lo]
+    if ctx.dist is not None:
+        parts = [None] * ctx.world
+        ctx.dist.all_gather_object(parts, local)        # the shards are contiguous row blocks in rank order
+        local = np.concatenate(parts, 0)
+    if ctx.rank == 0:
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "out.npy"), np.ascontiguousarray(local, np.float32))
+        if rows is not None:
+            np.save(os.path.join(path, "out_rows.npy"), rows.astype(np.float64))
 
 
 def time_region(fn, steps, sync, barrier):
@@ -1038,6 +1079,8 @@ def main():
     for i in range(args.warmup):
         step(i)
     wall = ctx.max_over_ranks(time_region(step, args.steps, ctx.sync, ctx.barrier))
+    if args.dump_outputs:
+        dump_outputs(ctx, job, args.dump_outputs)
     builds = len([i for i in range(args.steps) if i % args.rebuild_every == 0])
     mvms_per_s = args.steps / wall
     value = mvms_per_s                            # always the plain rate of the n_total-point operator
@@ -1064,8 +1107,14 @@ def main():
         "mvms_per_s": round(mvms_per_s, 2),
         "host_threads": host_threads,      # torch's BLAS pool after solvers.cap_host_threads() (half the cgroup CPU quota)
     }
-
     if multi:
+        result["rccl_ranks"] = dist.get_world_size()
+        result["backend"] = args.backend
+
+    if not args.full:
+        # a plain run reports the headline only; every other leg runs with --full
+        job.close()
+    elif multi:
         # ---- what the ranks spent where, the exchange, and the other scaling curves
         leg_wall = {"main": round(time.perf_counter() - T_START, 2)}       # wall seconds per leg on rank 0 (import + data + timed region so far)
 
@@ -1076,8 +1125,6 @@ def main():
             leg_wall[name] = round(time.perf_counter() - t0, 2)
             log(f"bench.py: leg {name}: {leg_wall[name]} s")
             return val
-        result["rccl_ranks"] = dist.get_world_size()
-        result["backend"] = args.backend
         result["warm_mvms_per_s"] = round(job.rate(args.steps), 1)
         result["stage_us"] = job.stage_us(20)
         result["exchange"] = exchange_record(job, vd, result["stage_us"])

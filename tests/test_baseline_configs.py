@@ -488,7 +488,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     dump = str(tmp_path / "dump")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--points", "30000",
-           "--rebuild-every", "2", "--backend", "gloo", "--skip-configs", "--dump", dump, "--scaling", "weak"]
+           "--rebuild-every", "2", "--backend", "gloo", "--skip-configs", "--dump", dump, "--scaling", "weak", "--full"]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -524,7 +524,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
 
 
 def test_bench_multi_rank_full_legs_rehearsal():
-    """The driver's multi-GPU command with EVERY leg -- `python bench.py --gpus N --steps 20 --warmup 5` -- rehearsed with
+    """The driver's multi-GPU command with EVERY leg -- `python bench.py --gpus N --steps 20 --warmup 5 --full` -- rehearsed with
     N = 4 gloo ranks on the one GPU (the GPU boxes admit at most 6 processes on a card, so the 8-rank command itself cannot
     be rehearsed here; nothing in bench.py depends on the rank count beyond the shard bounds), the fixed-size legs shrunk
     through PLX_BENCH_CONFIG4_POINTS.  One JSON line, rc 0, every leg present with its exchange record
@@ -532,7 +532,7 @@ def test_bench_multi_rank_full_legs_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PLX_BENCH_CONFIG4_POINTS"] = "200000"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "20", "--warmup", "5", "--points", "100000",
-           "--backend", "gloo"]
+           "--backend", "gloo", "--full"]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -571,7 +571,8 @@ def test_bench_single_rank_rccl_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PLX_BENCH_SINGLE_RANK_RCCL"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--points", "200000", "--skip-configs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--points", "200000", "--skip-configs",
+           "--full"]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     res = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
@@ -581,11 +582,12 @@ def test_bench_single_rank_rccl_rehearsal():
 
 
 def test_bench_single_gpu_json_contract():
-    """`python bench.py --steps K --warmup W` (the driver's N = 1 command): ONE JSON line with the contract keys, the
+    """`python bench.py --steps K --warmup W --full` (the driver's N = 1 command with every leg): ONE JSON line with the contract keys, the
     roofline object of the dominant stage (algorithmic bytes over a launch time measured in this run, PMC traffic from
     the committed profile) and the CPU baseline of the reference path on this host."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--skip-configs", "--skip-fine"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--skip-configs", "--skip-fine",
+           "--full"]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -606,6 +608,45 @@ def test_bench_single_gpu_json_contract():
     cpu = res["cpu_baseline"]
     assert cpu["kind"] in ("reference", "port") and cpu["cores"] == 1 and cpu["value"] > 0 and cpu["sample"]
     assert res["config"]["builds_in_timed_region"] == 1
+
+
+def test_bench_plain_run_headline_and_outputs(tmp_path):
+    """A plain `python bench.py --steps K --warmup W --dump-outputs DIR`: ONE JSON line with the headline keys only (no leg
+    of --full), `ms_per_step` the time of one of the K timed steps, and DIR/out.npy the MVM output of the last timed step,
+    which matches the CPU oracle on the same seeded inputs; a second run with the same arguments writes the same output,
+    and two gloo ranks on the one GPU write the same rows of the same operator (gathered in row order)."""
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    n, d, ell = 100_000, 8, 1.0
+    outs = []
+    for run, ranks in enumerate(("1", "1", "2")):
+        dump = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", ranks, "--steps", "7", "--warmup", "2",
+               "--points", str(n), "--rebuild-every", "3", "--dump-outputs", str(dump)] + (["--backend", "gloo"] if ranks == "2" else [])
+        proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, proc.stdout
+        res = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+            assert key in res, key
+        for key in ("roofline", "stages", "fine", "cpu_baseline", "config3", "config4", "warm_mvms_per_s"):
+            assert key not in res, key
+        assert res["steps"] == 7 and res["warmup"] == 2 and res["config"]["builds_in_timed_region"] == 3
+        assert res["unit"] == "MVMs/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        assert res["ms_per_step"] > 0 and abs(res["value"] * res["ms_per_step"] / 1e3 - 1.0) < 0.02
+        assert sorted(os.listdir(dump)) == ["out.npy"]
+        out = np.load(dump / "out.npy")
+        assert out.dtype == np.float32 and out.shape == (n, 1)
+        outs.append(out)
+    x, v = bench.synth(n, d, 1)
+    oracle.set_exact_mode(False)
+    try:
+        want = oracle.filter(v.numpy(), (x / ell).numpy(), bench.RBF1)
+    finally:
+        oracle.set_exact_mode(True)
+    assert rel_l2(outs[0], want) <= 1e-5 and rel_l2(outs[2], want) <= 1e-5
+    assert rel_l2(outs[1], outs[0]) <= 1e-6
 
 
 def test_bench_train_step_phases_add_up(plx):

@@ -41,7 +41,7 @@ def main():
     for r in trace:
         dur[(short(r["Kernel_Name"]), int(r["Grid_Size_X"]))].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
     lines = ["# rocprofv3 summary (%s)" % os.path.basename(src.rstrip("/")), "",
-             "Trace: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 2 --skip-cpu-baseline --skip-configs`",
+             "Trace: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 2 --full --skip-cpu-baseline --skip-configs`",
              "(both lattice regimes in one process).  Durations in us.", "",
              "| kernel | grid (threads) | calls | mean us | min us |", "|---|---:|---:|---:|---:|"]
     for key, v in sorted(dur.items(), key=lambda kv: -sum(kv[1])):
