@@ -328,6 +328,28 @@ int plx_cg_update(float *d_x, float *d_r, const float *d_p, const float *d_ap, c
 int plx_cg_direction(float *d_p, const float *d_r, const float *d_beta, int64_t n, int vd, void *stream);
 
 /*
+ * The exact kernel MVM, evaluated on the fly (nothing N x N is stored): the yardstick the lattice approximates.
+ *   plx_exact_mvm:  out[i][c] = sum_j k(|x1_i - x2_j|^2) v[j][c]
+ *   plx_exact_grad: grad_x1[i][:] = sum_j 2 k'(|x1_i - x2_j|^2) (x1_i - x2_j) (g_i . v_j)
+ * x1 [n1][d], x2 [n2][d], v [n2][t], g and out [n1][t], grad_x1 [n1][d]: fp32, row-major, contiguous, device memory;
+ * positions already divided by the lengthscale.  1 <= n1, n2 < 2^31, 1 <= d <= PLX_MAX_DIM, t >= 1.  k is a profile of
+ * the squared distance d2 (the project's own, stencil.py): RBF exp(-d2) (not GPyTorch's exp(-d2 / 2)); Matern-nu with
+ * r = sqrt(d2): e^-r, (1 + sqrt3 r) e^-sqrt3 r, (1 + sqrt5 r + 5/3 r^2) e^-sqrt5 r.  A Matern-1/2 pair at r = 0 adds 0
+ * to the gradient.  grad_x2 is plx_exact_grad with the roles swapped (x1 <-> x2, g <-> v).
+ * Stateless: d_work is the caller's, at least plx_exact_work_bytes(n1, n2, d, t) bytes (monotone in every size, at most
+ * 16 MB; < 0 for sizes outside the limits), so nothing is allocated and the calls are graph-capturable.  Deterministic:
+ * no float atomics (a split j range is summed slice by slice in a fixed order).  Every argument is checked before any
+ * GPU work (PLX_ERR_INVALID, PLX_ERR_DIM for d).
+ */
+enum { PLX_PROFILE_RBF = 0, PLX_PROFILE_MATERN12 = 1, PLX_PROFILE_MATERN32 = 2, PLX_PROFILE_MATERN52 = 3 };
+int64_t plx_exact_work_bytes(int64_t n1, int64_t n2, int d, int t);
+int plx_exact_mvm(const float *d_x1, int64_t n1, const float *d_x2, int64_t n2, int d, int profile,
+                  const float *d_v, int t, float *d_out, void *d_work, int64_t work_bytes, void *stream);
+int plx_exact_grad(const float *d_x1, int64_t n1, const float *d_x2, int64_t n2, int d, int profile,
+                   const float *d_g, const float *d_v, int t, float *d_grad_x1, void *d_work, int64_t work_bytes,
+                   void *stream);
+
+/*
  * Preconditioned batched CG: the reference trains with gpytorch.settings.max_preconditioner_size(100)
  * (experiments/train_simplexgp.py:36, configs/simplexgp.yml), i.e. every solve of (s K + sigma^2 I) is preconditioned by
  * P = L L^T + sigma^2 I, L [n][k] the rank-k pivoted Cholesky factor of s K (GPyTorch builds and applies it with torch

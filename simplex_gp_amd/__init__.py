@@ -2,8 +2,11 @@
 
 Public names mirror the reference package (gpytorch_lattice_kernel/__init__.py:1):
 RBFLattice, MaternLattice (+ BilateralKernel), plus the native boundary
-`filter(src, ref, coeffs)` and the staged `Lattice` handle.
+`filter(src, ref, coeffs)` and the staged `Lattice` handle.  The exact kernel MVM the
+lattice approximates (exact.py: exact_matmul, RBFExact / MaternExact, exact_twin,
+mvm_error) runs on the GPU too.
 """
+from .exact import ExactKernel, ExactLazyKernel, MaternExact, RBFExact, exact_matmul, exact_twin, mvm_error  # noqa: F401
 from .lattice import Lattice, filter  # noqa: F401
 from .lattice_kernel import (  # noqa: F401
     BilateralKernel,
@@ -22,4 +25,5 @@ __all__ = [
     "RBFLattice", "MaternLattice", "BilateralKernel", "LatticeAccelerated", "LatticeFilterGeneral",
     "SquareLazyLattice", "RectangularLazyLattice", "DiscretizedKernelFN", "get_coeffs", "rbf", "matern",
     "Matern", "Lattice", "filter", "lattice_cache",
+    "exact_matmul", "ExactLazyKernel", "ExactKernel", "RBFExact", "MaternExact", "exact_twin", "mvm_error",
 ]

@@ -18,7 +18,8 @@ ARRAY_KEYS, ARRAY_ENTRY_VERTEX, ARRAY_ENTRY_WEIGHT, ARRAY_NEIGHBORS = 0, 1, 2, 3
 ARRAY_ROW_PTR, ARRAY_CSR_POINT, ARRAY_CSR_WEIGHT, ARRAY_POINT_PERM = 4, 5, 6, 7
 MAX_DIM, MAX_ORDER = 32, 8
 FACTOR_F32, FACTOR_F16 = 0, 1
-ABI_VERSION = (0, 8)      # (major, minor) of plx_version() the signatures below belong to
+PROFILE_RBF, PROFILE_MATERN12, PROFILE_MATERN32, PROFILE_MATERN52 = 0, 1, 2, 3
+ABI_VERSION = (0, 9)      # (major, minor) of plx_version() the signatures below belong to
 
 
 class PlxError(RuntimeError):
@@ -82,6 +83,9 @@ _SIGNATURES = {
     "plx_cg_step_direction": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i64, _i32, _vp, _vp, _vp]),
     "plx_cg_update": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "plx_cg_direction": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "plx_exact_work_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "plx_exact_mvm": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "plx_exact_grad": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
     "plx_pcg_work_floats": (_i64, [_i64, _i32, _i32]),
     "plx_pcg_project": (_i32, [_vp, _i32, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "plx_pcg_apply": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

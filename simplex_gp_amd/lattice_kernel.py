@@ -379,16 +379,22 @@ class LatticeAccelerated(Kernel):
         return RectangularLazyLattice(scaled1, scaled2, self.dkernel_fn)
 
 
-def _lattice_kernel_factory(profile, default_order):
+# The factories record the profile's name on the kernel they return (`profile`, exact.PROFILES), so that
+# exact.exact_twin can find the exact kernel a lattice kernel approximates; a kernel built from any other callable has none.
+def _lattice_kernel_factory(profile, default_order, name):
     def make(*args, order=default_order, **kwargs):
-        return LatticeAccelerated(profile, *args, order=order, **kwargs)
+        k = LatticeAccelerated(profile, *args, order=order, **kwargs)
+        k.profile = name
+        return k
     return make
 
 
-RBFLattice = _lattice_kernel_factory(rbf, 2)                    # py:247-248
+RBFLattice = _lattice_kernel_factory(rbf, 2, "rbf")             # py:247-248
 RBFLattice.__name__ = "RBFLattice"
 BilateralKernel = RBFLattice                                    # py:250-251
 
 
 def MaternLattice(*args, nu=1.5, order=3, **kwargs):            # py:253-254
-    return LatticeAccelerated(lambda d2: Matern.apply(d2, nu), *args, order=order, **kwargs)
+    k = LatticeAccelerated(lambda d2: Matern.apply(d2, nu), *args, order=order, **kwargs)
+    k.profile = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}.get(nu)
+    return k
