@@ -8,7 +8,7 @@ build reproduces bit for bit, found without HIP.  From it the linear operator is
     K64 = S B_d ... B_0 S^T / (1 + 2^-d)
 
 i.e. the oracle's splat / blur / slice with every sum carried in float64 (the weights themselves are the build's fp32
-values).  backward64 is the position gradient of out = K(x) src (py:113-123) on top of it, stack and contraction in
+values).  terms64 is the size of the terms each entry of K64 v sums, the yardstick of a per-entry error.  backward64 is the position gradient of out = K(x) src (py:113-123) on top of it, stack and contraction in
 float64, together with the size of the terms that the gradient is a difference of.
 
 Checker only: the product and the GPU path never import it.
@@ -79,6 +79,15 @@ class Lattice64:
             vals = B @ vals
         return (self.S @ vals) / self.denom
 
+    def terms64(self, v):
+        """|S| |B_d| ... |B_0| |S^T| |v| / denom: row i bounds the sum of the magnitudes of every product that entry i of
+        K v adds up (so |K64 v| <= terms64(v) elementwise, with equality for non-negative v and taps).  An fp32 kernel that
+        carries each sum in fp32 stays within a small multiple of its rounding unit times this, row by row."""
+        vals = abs(self.S.T) @ np.abs(np.asarray(v, np.float64))
+        for B in self.blurs:
+            vals = abs(B) @ vals
+        return (abs(self.S) @ vals) / self.denom
+
 
 def stack64(g, src, x):
     """[g | g (x) x | src | src (x) x] in float64 (py:113-119): n x 2L(1+d), l-major within each product block."""
@@ -125,6 +134,17 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
+def entry_ratio(got, want, T):
+    """max_i |got - want|_i / T_i over every entry: the per-entry error in units of the size of the terms it sums.  Where
+    T_i = 0 (no term reaches the entry: an isolated vertex of a zero input) got_i must be exactly 0, else the ratio is inf."""
+    got, want, T = (np.asarray(a, np.float64) for a in (got, want, T))
+    err = np.abs(got - want)
+    zero = T == 0
+    if np.any(err[zero] != 0) or not np.all(np.isfinite(got)):
+        return float("inf")
+    return float((err[~zero] / T[~zero]).max()) if np.any(~zero) else 0.0
+
+
 def grad_x_ratios(got, want, T):
     """(||got - want|| / ||T||, rel-L2 or None): the second only where the gradient does not vanish
     (||want|| >= 0.1 ||T||), where a relative bar means something."""
@@ -145,7 +165,9 @@ def cloud(kind, n, d, seed=0, coeffs=None):
     simplex   every point inside one simplex (long vertex rows: n points on each of d+1 vertices);
     isolated  points so far apart that no two share a vertex or a blur neighbour: the true position gradient is 0
               (their lattice coordinates stay within int16 keys: the spacing is set by the taps' scale factors);
-    dup       a Gaussian cloud of n // 3 distinct points, each repeated."""
+    dup       a Gaussian cloud of n // 3 distinct points, each repeated;
+    grid      points on a coarse grid of half-integer coordinates (ties: many points on the same spot, others on the
+              boundaries between simplices)."""
     rng = np.random.default_rng(seed)
     if kind.startswith("gauss"):
         return (rng.standard_normal((n, d)) * float(kind[5:])).astype(np.float32)
@@ -176,4 +198,6 @@ def cloud(kind, n, d, seed=0, coeffs=None):
     if kind == "dup":
         base = rng.standard_normal((max(1, n // 3), d))
         return base[rng.integers(0, base.shape[0], n)].astype(np.float32)
+    if kind == "grid":
+        return (rng.integers(-3, 4, (n, d)) * 0.5).astype(np.float32)
     raise ValueError(kind)

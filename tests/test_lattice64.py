@@ -6,7 +6,7 @@ import torch
 
 import simplex_gp_amd as plx
 from oracle import oracle
-from tests.lattice64 import Lattice64, backward64, cloud, contract64, grad_x_ratios, rel_l2, stack64
+from tests.lattice64 import Lattice64, backward64, cloud, contract64, entry_ratio, grad_x_ratios, rel_l2, stack64
 
 PROFILES = {"rbf": plx.rbf, "matern15": lambda d2: plx.Matern.apply(d2, 1.5)}
 _TAPS = {}
@@ -137,3 +137,86 @@ def test_contract64_by_hand():
                 t += 2 * sum(abs(q) for q in parts)
             assert abs(gx[p, k] - want) <= 1e-12 and abs(T[p, k] - t) <= 1e-12
     assert np.array_equal(gs, f[:, :L])
+
+
+def taps_of_order(order, asym=False):
+    """2 * order + 1 taps: a Gaussian profile, or (asym) a lopsided one with a centre tap other than 1."""
+    half = np.exp(-0.5 * (np.arange(1, order + 1) * 0.7) ** 2)
+    if not asym:
+        return np.concatenate([half[::-1], [1.0], half]).astype(np.float32)
+    return np.concatenate([0.6 * half[::-1], [0.8], 1.1 * half]).astype(np.float32)
+
+
+@pytest.mark.parametrize("d", [1, 2, 3, 5, 8, 17, 32])
+def test_terms64_bounds_the_product(d):
+    """|K64 v| <= terms64(v) for signed v, equality (to rounding) for non-negative v (the taps are positive)."""
+    rng = np.random.default_rng(40 + d)
+    n = 83
+    for order, c in ((0, np.array([0.7], np.float32)), (1, taps_of_order(1)), (2, np.array([0.2, 0.5, 1.0, 0.4, 0.1], np.float32)),
+                     (3, taps_of_order(3, asym=True))):
+        for kind in ("gauss0.3", "gauss1", "simplex", "isolated"):
+            x = cloud(kind, n, d, seed=d, coeffs=c)
+            lat = Lattice64(x, c)
+            v = rng.standard_normal((n, 4))
+            T = lat.terms64(v)
+            assert T.shape == (n, 4)
+            assert np.all(np.abs(lat.apply(v)) <= T * (1 + 1e-12) + 1e-300), (order, kind)
+            a = np.abs(v)
+            assert np.allclose(lat.terms64(a), lat.apply(a), rtol=1e-12, atol=0), (order, kind)
+
+
+def test_entry_ratio():
+    """Per entry, in units of the entry's own terms; an entry with no terms must be exactly 0."""
+    want = np.array([[1.0, 0.0], [-2.0, 0.0]])
+    T = np.array([[2.0, 0.0], [4.0, 1.0]])
+    assert entry_ratio(want, want, T) == 0.0
+    got = want + np.array([[1e-6, 0.0], [0.0, 3e-7]])
+    assert entry_ratio(got, want, T) == pytest.approx(5e-7)
+    assert entry_ratio(want + np.array([[0.0, 1e-30], [0.0, 0.0]]), want, T) == float("inf")
+    assert entry_ratio(np.array([[np.nan, 0.0], [-2.0, 0.0]]), want, T) == float("inf")
+
+
+@pytest.mark.parametrize("order", range(9))
+def test_k64_columns_are_the_oracle_on_one_hot_inputs(order):
+    """Column j of K64 is oracle.filter of the j-th unit vector, for every order the ABI takes (0..8): order 0 has no
+    neighbour table at all, orders 5..8 have 10..16 neighbour slots per axis.  Symmetric and lopsided taps."""
+    for d, kind in ((1, "gauss1"), (2, "gauss0.3"), (3, "gauss1"), (6, "gauss0.3"), (3, "simplex")):
+        for asym in (False, True):
+            c = taps_of_order(order, asym)
+            n = 40
+            x = cloud(kind, n, d, seed=order + d, coeffs=c)
+            lat = Lattice64(x, c)
+            cols = np.array([0, 1, n // 2, n - 1])
+            e = np.zeros((n, cols.size), np.float32)
+            e[cols, np.arange(cols.size)] = 1.0
+            want = oracle_filter(e, x, c).astype(np.float64)
+            got = lat.matrix()[:, cols]
+            assert entry_ratio(got, want, lat.terms64(e)) <= 1e-6, (order, d, kind, asym)
+            assert rel_l2(got, want) <= 1e-6, (order, d, kind, asym)
+            assert np.array_equal(lat.apply(e), got)
+    # the taps really reach that far: a lopsided order-8 blur differs from its mirror image
+    c = taps_of_order(8, asym=True)
+    x = cloud("gauss1", 40, 2, seed=1)
+    v = np.random.default_rng(0).standard_normal((40, 1))
+    assert rel_l2(Lattice64(x, c[::-1].copy()).apply(v), Lattice64(x, c).apply(v)) > 1e-3
+
+
+def test_forward_families_name_every_kernel_literal():
+    """Every kernel family name the sources can report (each string literal assigned to kn_splat / kn_blur / kn_slice in
+    simplex_gp_amd/csrc/*.hip) is a stage of some family in tests/test_forward_fp64.FAMILIES, and FAMILIES names nothing
+    else: a new family cannot go unchecked.  The empty name (a stage with no owned rows or no corners launches nothing)
+    is not a family."""
+    import glob
+    import os
+    import re
+    from tests.test_forward_fp64 import FAMILIES, NAMES
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    literals = set()
+    for path in sorted(glob.glob(os.path.join(root, "simplex_gp_amd", "csrc", "*.hip"))):
+        text = open(path).read()
+        for stmt in re.finditer(r"\bkn_(?:splat|blur|slice)\s*=([^;]*);", text):
+            literals.update(re.findall(r'"([^"]*)"', stmt.group(1)))
+    literals.discard("")
+    assert len(literals) >= 30
+    assert literals == NAMES, {"in the sources only": sorted(literals - NAMES), "in FAMILIES only": sorted(NAMES - literals)}
+    assert all(len(f) == 3 for f in FAMILIES)
