@@ -221,6 +221,45 @@ int plx_slice(plx_lattice *lat, const float *d_values, int vd, float *d_out, voi
 int plx_apply(plx_lattice *lat, const float *d_src, int vd, float *d_out, void *stream);
 
 /*
+ * The rectangular product K(A, B) v -- splat and slice by ROW RANGE (libplx 0.9.1).  Prediction applies the operator
+ * between two different point sets (RectangularLazyLattice, bilateral_kernel.py:142-160: K(x*, X) alpha); the reference
+ * pads the right-hand side with zeros over the stacked points [X; x*], filters all of them and throws the rows of X away.
+ * Here the lattice is still built over the stacked points, and these calls splat only the rows that carry a right-hand
+ * side and slice only the rows that are wanted:
+ *   plx_splat_rows  d_values[m][stride] = S^T restricted to the caller's rows [row_begin, row_begin + row_count): d_src is
+ *                   [row_count][vd].  Every row of d_values is written (vertices no such point touches get 0).
+ *   plx_slice_rows  d_out[row_count][vd] = rows [row_begin, row_begin + row_count) of S d_values / (1 + 2^-d).
+ *   plx_apply_rows  splat_rows -> plx_blur -> slice_rows on the lattice's own workspace:
+ *                   d_out[out_count][vd] = K[out rows, src rows] d_src[src_count][vd],
+ * i.e. rows [out_begin, out_begin + out_count) of plx_apply applied to the n-row matrix that holds d_src in rows
+ * [src_begin, src_begin + src_count) and zeros elsewhere.  The two ranges are independent (disjoint, equal, nested,
+ * overlapping); the full range on both ends is plx_apply.  Swapping them is the transpose, K(B, A) g: the gradient of
+ * the product with respect to its right-hand side.
+ * Rows are ALWAYS in the caller's order, whatever plx_set_row_order says.  d_src / d_out need 4-byte alignment only;
+ * d_values is 16-byte aligned when vd > 1 (PLX_ERR_INVALID otherwise).
+ * Lattices built by plain plx_build (or plx_filter) over n points as a single shard: a sharded or merged lattice, and a
+ * build that replayed "reference_growth", return PLX_ERR_STATE.  Every argument is checked before any GPU work: NULL
+ * pointers, vd < 1, row_count < 1, a range outside [0, n) are PLX_ERR_INVALID; the 2^31 element limits of plx_apply hold
+ * for m * stride and row_count * stride (PLX_ERR_TOO_LARGE).
+ * Deterministic: no float atomics; two calls with the same arguments are bit-equal.
+ * Tables: what a range needs (the vertex-sorted corners of its rows, a stable compaction of the splat CSR; the lattice
+ * positions of its rows, ascending) is built by the first call that uses that (row_begin, row_count), on that call's
+ * stream, without any read-back, and kept until the lattice's next build; four ranges are kept at once (a product and its
+ * transpose alternate on the same lattice), the least recently used one is recycled.  From the second call with the same
+ * range and width on, a rows call neither allocates nor synchronises (plx_device_bytes does not move) and is
+ * graph-capturable; under stream capture a call that would have to build a table returns PLX_ERR_STATE.
+ * plx_last_rows_kernels: "splat=...;slice=..." of the last rows call on this lattice (plx_last_kernels goes on naming
+ * the square stages; the blur inside plx_apply_rows reports there).
+ */
+int plx_splat_rows(plx_lattice *lat, const float *d_src, int64_t row_begin, int64_t row_count, int vd,
+                   float *d_values, void *stream);
+int plx_slice_rows(plx_lattice *lat, const float *d_values, int vd, int64_t row_begin, int64_t row_count,
+                   float *d_out, void *stream);
+int plx_apply_rows(plx_lattice *lat, const float *d_src, int64_t src_begin, int64_t src_count, int vd,
+                   float *d_out, int64_t out_begin, int64_t out_count, void *stream);
+int plx_last_rows_kernels(const plx_lattice *lat, char *buf, int cap);
+
+/*
  * The reference's one-shot call (cpp:6-10 -> h:259-340): build a lattice for
  * d_ref, apply it to d_src, leave nothing behind.  `scratch` may be NULL or a
  * lattice object whose buffers are reused (avoids hipMalloc in steady state; it

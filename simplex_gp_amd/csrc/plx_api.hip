@@ -77,12 +77,16 @@ void release(DevBuf &b)
 
 static std::vector<DevBuf *> all_bufs(plx_lattice *L)
 {
-    return {&L->eslot, &L->flagmask, &L->blockcnt, &L->table, &L->counters,
+    std::vector<DevBuf *> v = {&L->eslot, &L->flagmask, &L->blockcnt, &L->table, &L->counters,
             &L->sort_keys_in, &L->slotmap, &L->nibmap, &L->prank, &L->vaxis, &L->vs0, &L->vowner, &L->ew_splat, &L->replay_vat, &L->replay_list, &L->replay_invisible, &L->replay_keys, &L->active_list, &L->active_cnt, &L->oh_pos, &L->oh_list, &L->oh_cnt, &L->ex_vid, &L->ex_pt, &L->ex_w, &L->ex_keys, &L->sort_vals_in, &L->sort_vals_out, &L->sort_temp,
             &L->vkeys, &L->ew, &L->evid, &L->nbr, &L->csr_pt, &L->csr_row, &L->csr_w, &L->csr_vid, &L->row_ptr,
             &L->head_partial, &L->tail_partial, &L->val_a, &L->val_b, &L->ssrc, &L->rec, &L->perm, &L->iota, &L->cmask, &L->cbase, &L->cids, &L->merge_slot, &L->merge_flags,
             &L->sortkey_in, &L->sortkey_out,
-            &L->bc_pt, &L->bc_w, &L->srow, &L->brow_ptr, &L->brow_vid, &L->s2_idx, &L->s2_ptr, &L->s2_vid, &L->s2_wave, &L->s2_wave_v, &L->partial, &L->pair_nbr, &L->inv_perm, &L->vslot, &L->vkeys_alt, &L->vslot_alt, &L->vorder};
+            &L->bc_pt, &L->bc_w, &L->srow, &L->brow_ptr, &L->brow_vid, &L->s2_idx, &L->s2_ptr, &L->s2_vid, &L->s2_wave, &L->s2_wave_v, &L->partial, &L->pair_nbr, &L->inv_perm, &L->vslot, &L->vkeys_alt, &L->vslot_alt, &L->vorder,
+            &L->rows_cnt, &L->rows_vid};
+    for (auto &r : L->rows)
+        for (DevBuf *b : {&r.ptr, &r.row, &r.w, &r.pos, &r.prow}) v.push_back(b);
+    return v;
 }
 
 struct DeviceGuard {
@@ -119,7 +123,7 @@ const char *plx_strerror(int code)
 const char *plx_last_error(void) { return g_err; }
 
 /* minor = the round that last extended the C ABI */
-const char *plx_version(void) { return "libplx 0.9.0 gfx950"; }
+const char *plx_version(void) { return "libplx 0.9.1 gfx950"; }
 
 int plx_create(int device, plx_lattice **out)
 {
@@ -182,6 +186,7 @@ static int build_entry(plx_lattice *L, const float *d_ref, int64_t n, int d, con
     L->tn = g_tune_defaults;       // the snapshot of the process defaults this build (and every later call on it) runs under:
                                    // taken only once the arguments are accepted -- a rejected call leaves a built lattice as it was
     L->built = false;
+    L->build_gen++;                // the row-range tables of earlier builds (plx_rows.hip) are stale from here on
     L->local_ready = false;
     L->single_use = single_use;
     L->n = n; L->d = d; L->ntaps = ntaps; L->order = ntaps / 2;
@@ -219,6 +224,7 @@ int plx_build_local(plx_lattice *L, const float *d_ref_local, int64_t n_local, i
     if (!g.ok) { set_error("plx_build_local: cannot select device %d", L->device); return PLX_ERR_HIP; }
     L->tn = g_tune_defaults;
     L->built = false;
+    L->build_gen++;
     L->local_ready = false;
     L->n = n_local; L->d = d; L->ntaps = ntaps; L->order = ntaps / 2;
     L->shard_index = 0; L->n_shards = 1;
@@ -447,6 +453,88 @@ static int apply_common(plx_lattice *L, const float *d_src, int vd, float *d_out
     int in_b = 0;
     PLX_TRY(blur_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), vd, &in_b, s));
     return slice_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, d_out, s, d_affine, d_src);
+}
+
+// ---- the rectangular product: splat / slice by row range (kernels and tables: plx_rows.hip) ----------------------------
+
+// Everything a rows call checks before any GPU work.  `a` / `b`: the call's two buffers.
+static int check_rows(const plx_lattice *L, const void *a, const void *b, int vd, int64_t begin, int64_t count,
+                      const char *who)
+{
+    if (!L || !a || !b) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
+    if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    if (count < 1 || begin < 0 || begin > L->n || count > L->n - begin) {
+        set_error("%s: rows [%lld, %lld + %lld) are not a non-empty range inside [0, %lld)", who, (long long)begin,
+                  (long long)begin, (long long)count, (long long)L->n);
+        return PLX_ERR_INVALID;
+    }
+    if (L->n_shards != 1 || L->partial_cover) {
+        set_error("%s: sharded or merged lattice (row ranges are served by plain single-shard builds only)", who);
+        return PLX_ERR_STATE;
+    }
+    if (L->replay.active) {
+        set_error("%s: this build replayed \"reference_growth\" (its splat and slice sides differ); row ranges are not "
+                  "served on it", who);
+        return PLX_ERR_STATE;
+    }
+    if ((int64_t)L->m * values_stride(vd) >= (1ll << 31) || count * values_stride(vd) >= (1ll << 31)) {
+        set_error("%s: m*vd or rows*vd exceeds 2^31 elements; split the columns", who);
+        return PLX_ERR_TOO_LARGE;
+    }
+    return PLX_OK;
+}
+
+static int check_values_aligned(const void *d_values, int vd, const char *who)
+{
+    if (vd > 1 && ((uintptr_t)d_values & 15) != 0) {
+        set_error("%s: d_values must be 16-byte aligned (vertex rows are whole 16-byte vectors)", who);
+        return PLX_ERR_INVALID;
+    }
+    return PLX_OK;
+}
+
+int plx_splat_rows(plx_lattice *L, const float *d_src, int64_t row_begin, int64_t row_count, int vd, float *d_values,
+                   void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_rows(L, d_src, d_values, vd, row_begin, row_count, "plx_splat_rows"));
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_splat_rows"));
+    DeviceGuard g(L->device);
+    return splat_rows_impl(L, d_src, row_begin, row_count, vd, d_values, (hipStream_t)stream);
+}
+
+int plx_slice_rows(plx_lattice *L, const float *d_values, int vd, int64_t row_begin, int64_t row_count, float *d_out,
+                   void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_rows(L, d_values, d_out, vd, row_begin, row_count, "plx_slice_rows"));
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_slice_rows"));
+    DeviceGuard g(L->device);
+    return slice_rows_impl(L, d_values, vd, row_begin, row_count, d_out, (hipStream_t)stream);
+}
+
+int plx_apply_rows(plx_lattice *L, const float *d_src, int64_t src_begin, int64_t src_count, int vd, float *d_out,
+                   int64_t out_begin, int64_t out_count, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_rows(L, d_src, d_out, vd, src_begin, src_count, "plx_apply_rows (source rows)"));
+    PLX_TRY(check_rows(L, d_src, d_out, vd, out_begin, out_count, "plx_apply_rows (output rows)"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    PLX_TRY(ensure(L->val_a, (size_t)L->m * values_stride(vd) * 4));
+    PLX_TRY(ensure(L->val_b, (size_t)L->m * values_stride(vd) * 4));
+    PLX_TRY(splat_rows_impl(L, d_src, src_begin, src_count, vd, L->val_a.as<float>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), vd, &in_b, s));
+    return slice_rows_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, out_begin, out_count, d_out, s);
+}
+
+int plx_last_rows_kernels(const plx_lattice *L, char *buf, int cap)
+{
+    if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
+    snprintf(buf, (size_t)cap, "splat=%s;slice=%s", L->kn_rows_splat, L->kn_rows_slice);
+    return PLX_OK;
 }
 
 int plx_apply_backward(plx_lattice *L, const float *d_g, const float *d_src, const float *d_ref, int nrhs,

@@ -292,6 +292,25 @@ struct plx_lattice {
     // kernels launched by the last splat / blur / slice on this lattice (names as rocprofv3 shows them, '+'-joined)
     const char *kn_splat = "", *kn_blur = "", *kn_slice = "";
 
+    // plx_splat_rows / plx_slice_rows / plx_apply_rows (plx_rows.hip): the tables of a range of caller rows, built by the
+    // first call that needs them, valid for the build they were made from
+    struct RowsRange {
+        int64_t begin = -1, count = 0;
+        uint64_t gen = 0;         // build_gen of the build the tables describe (0: empty slot)
+        uint64_t used = 0;        // rows_clock of the last call on this range (the least recently used slot is recycled)
+        bool splat_ready = false, slice_ready = false;
+        plx::DevBuf ptr;          // int32 [m+1]            corners of the range at vertex v: [ptr[v], ptr[v+1])
+        plx::DevBuf row;          // int32 [count (d+1)]    row - begin of every corner of the range, in ensure_csr's vertex order
+        plx::DevBuf w;            // float [count (d+1)]    its barycentric weight
+        plx::DevBuf pos;          // int32 [count]          lattice positions of the rows, ascending
+        plx::DevBuf prow;         // int32 [count]          row - begin of each
+    };
+    static constexpr int kRowsRanges = 4;     // a product and its transpose use two each when both ends differ
+    RowsRange rows[kRowsRanges];
+    uint64_t build_gen = 0, rows_clock = 0;   // builds started on this object; rows calls served
+    plx::DevBuf rows_cnt, rows_vid;           // int32 scratch of the table builds: per-tile counts, vertex of every kept corner
+    const char *kn_rows_splat = "", *kn_rows_slice = "";   // kernels of the last rows call (plx_last_rows_kernels)
+
     int32_t *h_pinned = nullptr;   // pinned host staging (exports)
     int *h_mail = nullptr;         // mailbox of read_back: coherent pinned host memory, word 0 = sequence number, then up to 62 values
     int mail_seq = 0;
@@ -364,6 +383,11 @@ int build_blur_pairs(plx_lattice *L, hipStream_t stream);   // composite neighbo
 int ensure_blur_pairs(plx_lattice *L, hipStream_t stream);  // ... built on first use (multi-column blurs, plx_filter_onehot)
 int slice_impl(plx_lattice *L, const float *d_values, int vd, float *d_out, hipStream_t stream,
                const float *d_affine = nullptr, const float *d_src = nullptr, float *d_dot_partial = nullptr);
+// plx_rows.hip: splat / slice restricted to the caller's rows [begin, begin + count) (arguments checked by the entry points)
+int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t count, int vd, float *d_values,
+                    hipStream_t stream);
+int slice_rows_impl(plx_lattice *L, const float *d_values, int vd, int64_t begin, int64_t count, float *d_out,
+                    hipStream_t stream);
 // plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
 int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,

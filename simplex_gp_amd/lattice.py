@@ -60,6 +60,7 @@ class Lattice:
         self.lattice_rows = False
         self._dot_work = None
         self.build_id = 0         # counts the builds of this object (holders of per-build data compare it)
+        self._merged = False      # built by build_local + build_merge (one rank's rows of a sharded lattice)
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -93,6 +94,7 @@ class Lattice:
                                     index, count, _stream_ptr(self.device))
         nv.check(rc, "plx_build")
         self.build_id += 1
+        self._merged = False
         self._ref = ref
         self.taps = taps
         self._perm_cache = None
@@ -118,6 +120,7 @@ class Lattice:
                                      ctypes.c_void_p(out.data_ptr()), _stream_ptr(self.device))
         nv.check(rc, "plx_filter")
         self.build_id += 1
+        self._merged = False
         self._ref, self.taps, self._perm_cache, self._own_begin = ref, taps, None, 0
         return out
 
@@ -136,6 +139,7 @@ class Lattice:
                                    _stream_ptr(self.device))
         nv.check(rc, "plx_build_local")
         self.build_id += 1
+        self._merged = True
         self._ref, self.taps, self._perm_cache, self._own_begin = ref_local, taps, None, 0
         keys = torch.empty((int(L.plx_local_vertices(self._h)), int(L.plx_key_words(d))), dtype=torch.int32,
                            device=self.device)
@@ -366,6 +370,78 @@ class Lattice:
                                     ctypes.c_void_p(out.data_ptr()), _stream_ptr(self.device))
         nv.check(rc, "plx_apply")
         return out
+
+    # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
+    def _rows(self, begin, count):
+        begin, count = int(begin), int(count)
+        if count < 1 or begin < 0 or begin + count > self.n:
+            raise ValueError(f"rows [{begin}, {begin + count}) are not a non-empty range inside [0, {self.n})")
+        return begin, count
+
+    def splat_rows(self, src, row_begin, values=None):
+        """values = S^T restricted to the caller's rows [row_begin, row_begin + len(src)); every vertex row is written."""
+        _check_f32_cuda(src, "src")
+        src = src.contiguous()
+        begin, count = self._rows(row_begin, src.shape[0])
+        vd = src.shape[1]
+        if values is None:
+            values = self.new_values(vd)
+        assert values.shape == (self.m, self.values_stride(vd)) and values.is_contiguous()
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_splat_rows(self._h, ctypes.c_void_p(src.data_ptr()), begin, count, vd,
+                                         ctypes.c_void_p(values.data_ptr()), _stream_ptr(self.device))
+        nv.check(rc, "plx_splat_rows")
+        return values
+
+    def slice_rows(self, values, row_begin, row_count, out=None, vd=None):
+        """out[row_count, vd] = rows [row_begin, row_begin + row_count) of S values / (1 + 2^-d)."""
+        _check_f32_cuda(values, "values")
+        vd = values.shape[1] if vd is None else vd
+        assert values.shape[1] == self.values_stride(vd) and values.is_contiguous()
+        begin, count = self._rows(row_begin, row_count)
+        if out is None:
+            out = torch.empty((count, vd), dtype=torch.float32, device=self.device)
+        assert out.shape == (count, vd) and out.is_contiguous()
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_slice_rows(self._h, ctypes.c_void_p(values.data_ptr()), vd, begin, count,
+                                         ctypes.c_void_p(out.data_ptr()), _stream_ptr(self.device))
+        nv.check(rc, "plx_slice_rows")
+        return out
+
+    def apply_rows(self, src, src_begin, out_begin, out_count, out=None):
+        """out[out_count, vd] = K[out rows, src rows] src: rows [out_begin, out_begin + out_count) of apply() of the
+        n-row matrix that holds `src` in rows [src_begin, src_begin + len(src)) and zeros elsewhere (plx_apply_rows).
+        Rows are in the caller's order whatever set_lattice_row_order() says."""
+        _check_f32_cuda(src, "src")
+        src = src.contiguous()
+        sb, sc = self._rows(src_begin, src.shape[0])
+        ob, oc = self._rows(out_begin, out_count)
+        vd = src.shape[1]
+        if out is None:
+            out = torch.empty((oc, vd), dtype=torch.float32, device=self.device)
+        assert out.shape == (oc, vd) and out.is_contiguous()
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_apply_rows(self._h, ctypes.c_void_p(src.data_ptr()), sb, sc, vd,
+                                         ctypes.c_void_p(out.data_ptr()), ob, oc, _stream_ptr(self.device))
+        nv.check(rc, "plx_apply_rows")
+        return out
+
+    def rows_kernels(self):
+        """Kernels launched by the last splat_rows / slice_rows (or apply_rows) on this lattice: {"splat": [...],
+        "slice": [...]}; the blur of apply_rows reports through stage_kernels()."""
+        buf = ctypes.create_string_buffer(256)
+        nv.check(nv.lib().plx_last_rows_kernels(self._h, buf, 256), "plx_last_rows_kernels")
+        out = {}
+        for part in buf.value.decode().split(";"):
+            k, _, names = part.partition("=")
+            out[k] = [x for x in names.split("+") if x]
+        return out
+
+    def accepts_rows(self):
+        """True when the rows calls serve this lattice: a plain single-shard build without the "reference_growth" replay."""
+        if self.n_owned != self.n or self._merged:
+            return False
+        return not self.reference_growth_info()["replayed"]
 
     def apply_affine(self, src, scale_shift, out=None, want_dot=False):
         """out = a * K src + b * src with (a, b) = scale_shift (a 2-element float32 tensor on the device, read

@@ -286,6 +286,38 @@ class LatticeFilterGeneral(Function):
         return grad_source, grad_reference, None
 
 
+class LatticeRowsProduct(Function):
+    """out = K[out rows, src rows] @ source on the lattice of `positions` (the stacked points of a rectangular operator):
+    only the rows that carry a right-hand side are splatted, only the wanted rows are sliced (plx_apply_rows).  The
+    gradient with respect to `source` is the transposed product on the same lattice, ranges swapped (K is treated as
+    symmetric, py:110-111).  No position gradient: RectangularLazyLattice keeps the padded path for that."""
+
+    @staticmethod
+    def forward(ctx, source, positions, coeffs, lat, src_begin, out_begin, out_count):
+        ctx.positions, ctx.coeffs = positions, coeffs
+        ctx.ranges = (int(src_begin), int(source.shape[0]), int(out_begin), int(out_count))
+        return lat.apply_rows(source, src_begin, out_begin, out_count)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        grad_source = None
+        if ctx.needs_input_grad[0]:
+            sb, sc, ob, oc = ctx.ranges
+            with torch.no_grad():
+                lat = _cache.get(ctx.positions, ctx.coeffs)       # the forward's lattice (rebuilt if it was evicted since)
+                grad_source = lat.apply_rows(grad_output.contiguous(), ob, sb, sc)
+        return grad_source, None, None, None, None, None, None
+
+
+def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1):
+    """Whether K(xin, xout) @ V goes through the native row-range product: a CUDA fp32 2-D right-hand side, no test hook /
+    foreign filter installed (LatticeFilterGeneral.method), no gradient wanted for the positions, the route switched
+    on (RectangularLazyLattice.native_rows) and, where the caller says how many columns V has, at least `min_columns`
+    of them (RectangularLazyLattice.native_min_columns).  Everything else takes the padded square filter."""
+    return bool(enabled and device_type == "cuda" and dtype == torch.float32 and dim == 2 and hook is None
+                and not requires_grad and (columns is None or columns >= min_columns))
+
+
 def _lattice_matvec(rhs, positions, dkernel):
     """K(positions) @ rhs through the autograd op; the one place the operator classes reach the native filter."""
     return LatticeFilterGeneral.apply(rhs, positions, dkernel)
@@ -316,7 +348,21 @@ class SquareLazyLattice(LazyTensor):
 class RectangularLazyLattice(LazyTensor):
     """K(xin, xout) for two different point sets (prediction), py:142-160: the right-hand side lives on `xout`; it is
     extended by zeros over `xin`, ONE square filter runs over the stacked points [xout; xin], and the rows that belong to
-    `xin` are returned."""
+    `xin` are returned.
+
+    native_rows: where rows_route() allows it, and the lattice of the stacked points is a plain single-shard build, the
+    product runs as plx_apply_rows on that lattice instead -- the rows of `xout` are splatted, the rows of `xin` sliced,
+    nothing is padded or thrown away -- and the transposed operator works on the SAME lattice with the two ranges swapped
+    (it does not build [xin; xout] again).  False: the padded path, always.
+
+    native_min_columns: the route is taken from this many columns of V on.  Measured at N = 1e6 + 2.5e5, d = 8
+    (profiles/rows_measured.md): at 101 columns (a prediction split) the native product is 10 % faster than the padded one
+    and needs 1.25 GB less; at 11 and at 1 column its vertex-gather splat loses to the square stages' tuned narrow kernels
+    (0.89 against 0.68 ms, 0.59 against 0.24 ms).  The crossover between 11 and 101 has not been located, so everything
+    below the measured winning width keeps the padded path."""
+
+    native_rows = True
+    native_min_columns = 101
 
     def __init__(self, xin, xout, dkernel=None):
         super().__init__(xin, xout, dkernel=dkernel)
@@ -328,6 +374,17 @@ class RectangularLazyLattice(LazyTensor):
     def _matmul(self, V):
         n_out, n_in = self.xout.shape[-2], self.xin.shape[-2]
         assert V.shape[-2] == n_out, f"mismatched shapes? {V.shape, self.xout.shape}"
+        wants_grad = torch.is_grad_enabled() and (self.xin.requires_grad or self.xout.requires_grad)
+        if rows_route(V.device.type, V.dtype, V.dim(), LatticeFilterGeneral.method, wants_grad, type(self).native_rows,
+                      V.shape[-1], type(self).native_min_columns):
+            base, swapped = self.__dict__.get("_rows_base", (self, False))
+            stacked = base._stacked_points()                       # [base.xout; base.xin]: one lattice for both directions
+            coeffs = self.dkernel.get_coeffs()
+            lat = _cache.get(stacked, coeffs)
+            if lat.accepts_rows():
+                nb_out = base.xout.shape[-2]
+                src_begin, out_begin = (nb_out, 0) if swapped else (0, nb_out)
+                return LatticeRowsProduct.apply(V, stacked, coeffs, lat, src_begin, out_begin, n_in)
         stacked_rhs = torch.nn.functional.pad(V, (0, 0, 0, n_in))          # zero rows for the points of xin
         return _lattice_matvec(stacked_rhs, self._stacked_points(), self.dkernel)[..., n_out:, :]
 
@@ -345,7 +402,10 @@ class RectangularLazyLattice(LazyTensor):
         return hit[1]
 
     def _transpose_nonbatch(self):
-        return type(self)(self.xout, self.xin, self.dkernel)
+        t = type(self)(self.xout, self.xin, self.dkernel)
+        base, swapped = self.__dict__.get("_rows_base", (self, False))
+        t.__dict__["_rows_base"] = (base, not swapped)             # the native route serves it from base's lattice
+        return t
 
 
 class LatticeAccelerated(Kernel):
