@@ -474,25 +474,18 @@ int64_t plx_export_bytes(const plx_lattice *lat, int which);
  * thread is inside a plx_* call on a built lattice does not disturb it (concurrent plx_tune and build calls still need
  * the caller's own ordering: the copy is a plain struct copy).  plx_lattice_tune changes a switch in ONE lattice's copy,
  * effective from its next call until its next build (A/B of MVM-side variants over the same tables).  Keys (default):
- *   "sort_points" (1; 0 keeps the caller's point order), "order_zcurve" (1; 0 = lexicographic point order, 2 = Z-curve of
- *   the blur-axis coordinates), "order_compact" (1 = point-order keys laid out over exactly the bits each coordinate's
- *   range needs; 0 = a fixed 7 bits per coordinate), "readback_spin" (1 = counts come back through the mailbox; 0 = stream
- *   synchronisation), "vertex_order" (1: vertices numbered along the Morton curve of their blur-axis coordinates where
+ *   "sort_points" (1; 0 keeps the caller's point order), "vertex_order" (1: vertices numbered along the Morton curve of their blur-axis coordinates where
  *   that pays, 65536 <= m <= 0.9 n (d+1); 0: always by first touch; 2: always Morton -- vertex ids are internal, the
  *   PLX_ARRAY_* exports are in whichever numbering the build used), "insert_dedupe" (2 = every key of a wave probes the table once: lanes with equal keys are grouped by hash ballots; 1 = runs of
- *   equal NEIGHBOURING lanes probe once; 0 = every lane probes), "insert_plane_fast" (1 = the
- *   d+1 corner planes of a run of points are adjacent workgroups of the hashed insert / neighbour lookups; 0 =
- *   plane-major launch order), "nbr_symmetric" (1), "compact_nbr" (1 = when under a quarter of the neighbour slots exist;
+ *   equal NEIGHBOURING lanes probe once; 0 = every lane probes), "compact_nbr" (1 = when under a quarter of the neighbour slots exist;
  *   0 never, 2 always), "blur_vpt" (4; vertices per thread at vd = 1: 2 or 4, anything else selects the general kernel),
  *   "blur_small" (1), "blur_narrow" (1), "blur_multi" (1 = the wide-row blur kernels from 17 chunks per row; 2 = from 32, the
  *   gate of rounds 1-5), "blur_fuse" (1), "blur_fuse_vec" (1 = two blur axes per launch
  *   for rows of 2..4 chunks; 0 = one), "splat_direct" (1), "splat_group" (1), "splat_wide" (1 = the row-parallel splat from 17 chunks per
- *   row; 2 = from 32), "xcd_remap" (1),
+ *   row; 2 = from 32),
  *   "block_path" (1 = block tables for vd = 1 when corners share vertices; 0 never, 2 whenever representable),
  *   "block_e" (0 = corners per thread of the block kernels chosen per lattice; 16 or 24: a block holds 256 * e corners),
- *   "block_dense_combine" (1), "scatter_store" (0), "unpermute_gather" (1), "nbr_window" (512: on Morton-numbered lattices a neighbour lookup first binary-searches this
- *   many sorted vertex codes next to the vertex -- found, or proven absent, without touching the hash table when the window
- *   brackets the target; 0 = hash table only), "nbr_bitmap" (1 = neighbour lookups test a
+ *   "block_dense_combine" (1), "unpermute_gather" (1), "nbr_bitmap" (1 = neighbour lookups test a
  *   slot-occupancy bitmap before the hash table when m >= 2^22; 0 never, 2 always), "splat_first" (1 = single-column splat by
  *   first-touch stores + a short extras list when m >= 0.9 nnz; 0 never, 2 whenever representable, 3 = 2 with scattered
  *   stores), "perm_rows" (1 = multi-column row permutations by 16-byte chunks / LDS-transposed whole-line stores; 0 = the
@@ -500,10 +493,19 @@ int64_t plx_export_bytes(const plx_lattice *lat, int which);
  *   running every lookup, the checker of 1), "blur_active" (1: wide rows on sparse lattices -- centre tap 1 -- blur only the vertices with a neighbour on the axis, in place; 0 never, 2 whenever representable),
  *   "contract_v" (1 = the fused backward's slice + contraction with the corner count
  *   compiled in; 0 = the run-time form),
- *   and the round-5 build switches "nbr_sliced" (1), "nbr_seed" (1), "assign_evid" (1), "insert_xcd" (2), "order_sample" (8),
- *   "embed_vrange" (0), "blk_sort" (15): DESIGN.md 2.  (Round 6 removed "hash_v", "table_fp", "flag_own" and "insert_v" with the
- *   measured-loser code paths behind them: the linear hash, fingerprints, own-mark flags and the point-per-thread insert
- *   are what every build uses.)
+ *   and the round-5 build switches "nbr_sliced" (1), "nbr_seed" (1), "assign_evid" (1): DESIGN.md 2.  (Round 6 removed
+ *   "hash_v", "table_fp", "flag_own" and "insert_v" with the measured-loser code paths behind them: the linear hash,
+ *   fingerprints, own-mark flags and the point-per-thread insert are what every build uses.  Twelve more settled A/B
+ *   levers went the same way later, each fixed at what had been its default: "xcd_remap" (tiles remapped so that every XCD
+ *   owns a contiguous eighth; the multi-item wide-row blur keeps plain order), "readback_spin" (counts come back through
+ *   the mailbox), "order_compact" (point-order keys over exactly the bits each coordinate's range needs), "order_zcurve"
+ *   (points along the Z-curve of their rounded lattice coordinates), "order_sample" (that range from every 8th point, from
+ *   65,536 points up), "embed_vrange" (the vertex-coordinate range comes from a pass of its own), "insert_xcd" (the hashed
+ *   insert in plain tile order, the id lookup remapped), "insert_plane_fast" (the d+1 axis planes of a run of vertices are
+ *   adjacent workgroups of the neighbour lookups wherever the grid allows), "nbr_symmetric" (positive taps looked up, hits
+ *   mirrored), "nbr_window" (on Morton-numbered lattices a neighbour lookup first binary-searches 512 sorted vertex codes
+ *   on the target's side of the vertex), "scatter_store" (plain stores out of the block slice) and "blk_sort" (block
+ *   tables sorted as packed keys, 5 bits per pass, 512 threads; (key, value) pairs where the packed key does not fit).)
  * The diagnostic ablations "splat_ablate" / "blur_ablate" / "block_ablate" exist only in libplx_diag.so (make diag).
  * Unknown keys return PLX_ERR_INVALID. */
 int plx_tune(const char *key, int value);

@@ -206,13 +206,13 @@ template <bool DENSE>
 __global__ __launch_bounds__(kBlock) void splat_combine_kernel(const int *__restrict__ s2_wave, const int *__restrict__ s2_wave_v,
                                                                const int *__restrict__ s2_idx, const int *__restrict__ s2_vid,
                                                                const float *__restrict__ partial, int nwaves,
-                                                               float *__restrict__ values, int ntiles, int remap,
+                                                               float *__restrict__ values, int ntiles,
                                                                int ablate)
 {
     // XCD-aware tile order: every XCD sweeps one contiguous eighth of the vertex-sorted rows, whose partials lie in
     // about one eighth of the partial array (blocks and vertices both follow the lattice order): L2-resident gathers
     ablate = PLX_DIAG_VALUE(ablate);
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int lane = threadIdx.x & 63;
     const int w = tile * (kBlock / 64) + (threadIdx.x >> 6);
@@ -337,13 +337,13 @@ int splat_block_impl(plx_lattice *L, const float *d_src, float *d_values, hipStr
     if (L->n_shards != 1 || L->partial_cover) PLX_HIP_TRY(hipMemsetAsync(d_values, 0, (size_t)L->m * 4, stream));
     const int nt = ceil_div(L->n_s2waves, kBlock / 64);
     if (dense)
-        splat_combine_kernel<true><<<tile_grid(nt, g_xcd_remap), kBlock, 0, stream>>>(
+        splat_combine_kernel<true><<<tile_grid(nt), kBlock, 0, stream>>>(
             L->s2_wave.as<int>(), L->s2_wave_v.as<int>(), L->s2_idx.as<int>(), L->s2_vid.as<int>(), L->partial.as<float>(),
-            (int)L->n_s2waves, d_values, nt, g_xcd_remap, PLX_DIAG_VALUE(g_block_ablate));
+            (int)L->n_s2waves, d_values, nt, PLX_DIAG_VALUE(g_block_ablate));
     else
-        splat_combine_kernel<false><<<tile_grid(nt, g_xcd_remap), kBlock, 0, stream>>>(
+        splat_combine_kernel<false><<<tile_grid(nt), kBlock, 0, stream>>>(
             L->s2_wave.as<int>(), L->s2_wave_v.as<int>(), L->s2_idx.as<int>(), L->s2_vid.as<int>(), L->partial.as<float>(),
-            (int)L->n_s2waves, d_values, nt, g_xcd_remap, PLX_DIAG_VALUE(g_block_ablate));
+            (int)L->n_s2waves, d_values, nt, PLX_DIAG_VALUE(g_block_ablate));
     L->kn_splat = "splat_block_kernel+splat_combine_kernel";
     tmark(L, stream);
     PLX_HIP_TRY(hipGetLastError());
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(kBlkT) void slice_block_kernel(const uint16_t *__re
                                                            const float *__restrict__ values, const uint32_t *__restrict__ perm,
                                                            int own_begin, int n_own, int P, float rden,
                                                            float *__restrict__ out, const float *__restrict__ affine,
-                                                           const float *__restrict__ src, int store_mode)
+                                                           const float *__restrict__ src)
 {
     extern __shared__ float lds_val[];                  // values of the block's rows
     const int tid = threadIdx.x;
@@ -389,9 +389,7 @@ __global__ __launch_bounds__(kBlkT) void slice_block_kernel(const uint16_t *__re
         for (int r = 0; r < D1; ++r) acc += w[r] * lds_val[v[r]] * rden;
         const int row = perm ? (int)perm[own_begin + p0 + i] - own_begin : p0 + i;
         if (affine) acc = affine[0] * acc + affine[1] * src[row];      // out = a K src + b src (plx_apply_affine)
-        if (store_mode == 1) __builtin_nontemporal_store(acc, out + row);
-        else if (store_mode == 2) __hip_atomic_store(out + row, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else out[row] = acc;
+        out[row] = acc;
         i += T;
         if (i < np) {
 #pragma unroll
@@ -557,8 +555,7 @@ int slice_block_impl(plx_lattice *L, const float *d_values, float *d_out, hipStr
     case D1:                                                                                                            \
         slice_block_kernel<D1><<<(unsigned)L->nblocks, kBlkT, lds, stream>>>(                                           \
             L->srow.as<uint16_t>(), L->srow_stride, L->ew.as<float>(), (int)L->n, L->brow_ptr.as<int>(),                \
-            L->brow_vid.as<int>(), d_values, perm, (int)L->own_begin, n_own, L->blk_P, rden, d_out, d_affine, d_src,   \
-            perm ? g_scatter_store : 0);                                                                                \
+            L->brow_vid.as<int>(), d_values, perm, (int)L->own_begin, n_own, L->blk_P, rden, d_out, d_affine, d_src);  \
         break;
         PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9)
         PLX_CASE(10) PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17)

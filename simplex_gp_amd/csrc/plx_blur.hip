@@ -15,13 +15,12 @@ template <int ORDER, int VPT>
 __global__ __launch_bounds__(kBlock) void blur_axis_v1_kernel(const float *__restrict__ old,
                                                               float *__restrict__ out,
                                                               const int *__restrict__ nbr, int m,
-                                                              int64_t mstride, TapArgs taps, int ablate, int ntiles,
-                                                              int remap)
+                                                              int64_t mstride, TapArgs taps, int ablate, int ntiles)
 {
     ablate = PLX_DIAG_VALUE(ablate);                   // diagnostics are compiled into libplx_diag.so only
     using ivec = typename std::conditional<VPT == 4, int4, int2>::type;
     using fvec = typename std::conditional<VPT == 4, float4, float2>::type;
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int i0 = (tile * kBlock + threadIdx.x) * VPT;
     if (i0 >= m) return;
@@ -202,11 +201,11 @@ __global__ __launch_bounds__(kBlock) void pair_nbr_kernel(const int *__restrict_
 template <int VPT>
 __global__ __launch_bounds__(kBlock) void blur_pair_v1_kernel(const float *__restrict__ old, float *__restrict__ out,
                                                               const int *__restrict__ pn, int m, int64_t mstride,
-                                                              TapArgs taps, int ntiles, int remap)
+                                                              TapArgs taps, int ntiles)
 {
     using ivec = typename std::conditional<VPT == 4, int4, int2>::type;
     using fvec = typename std::conditional<VPT == 4, float4, float2>::type;
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int i0 = (tile * kBlock + threadIdx.x) * VPT;
     if (i0 >= m) return;
@@ -274,11 +273,11 @@ __global__ __launch_bounds__(kBlock) void blur_pair_v1_kernel(const float *__res
 template <int ROWLEN>
 __global__ __launch_bounds__(kBlock) void blur_pair_narrow_kernel(const float4 *__restrict__ old, float4 *__restrict__ out,
                                                                   const int *__restrict__ pn, uint32_t total,
-                                                                  uint32_t mstride, TapArgs taps, int ntiles, int remap,
+                                                                  uint32_t mstride, TapArgs taps, int ntiles,
                                                                   int ablate)
 {
     ablate = PLX_DIAG_VALUE(ablate);                   // diagnostics are compiled into libplx_diag.so only
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const uint32_t item = (uint32_t)tile * kBlock + threadIdx.x;
     if (item >= total) return;
@@ -310,15 +309,15 @@ __global__ __launch_bounds__(kBlock) void blur_pair_narrow_kernel(const float4 *
 }
 
 static void launch_blur_pair_narrow(const float4 *cur, float4 *nxt, const int *pn, int m, int64_t mstride, int rowlen,
-                                    const TapArgs &taps, hipStream_t stream, int remap)
+                                    const TapArgs &taps, hipStream_t stream)
 {
     const uint32_t total = (uint32_t)m * (uint32_t)rowlen;
     const int nt = ceil_div((int64_t)total, kBlock);
-    const int grid = tile_grid(nt, remap);
+    const int grid = tile_grid(nt);
     switch (rowlen) {
-    case 2: blur_pair_narrow_kernel<2><<<grid, kBlock, 0, stream>>>(cur, nxt, pn, total, (uint32_t)mstride, taps, nt, remap, PLX_DIAG_VALUE(g_blur_ablate)); break;
-    case 3: blur_pair_narrow_kernel<3><<<grid, kBlock, 0, stream>>>(cur, nxt, pn, total, (uint32_t)mstride, taps, nt, remap, PLX_DIAG_VALUE(g_blur_ablate)); break;
-    default: blur_pair_narrow_kernel<4><<<grid, kBlock, 0, stream>>>(cur, nxt, pn, total, (uint32_t)mstride, taps, nt, remap, PLX_DIAG_VALUE(g_blur_ablate)); break;
+    case 2: blur_pair_narrow_kernel<2><<<grid, kBlock, 0, stream>>>(cur, nxt, pn, total, (uint32_t)mstride, taps, nt, PLX_DIAG_VALUE(g_blur_ablate)); break;
+    case 3: blur_pair_narrow_kernel<3><<<grid, kBlock, 0, stream>>>(cur, nxt, pn, total, (uint32_t)mstride, taps, nt, PLX_DIAG_VALUE(g_blur_ablate)); break;
+    default: blur_pair_narrow_kernel<4><<<grid, kBlock, 0, stream>>>(cur, nxt, pn, total, (uint32_t)mstride, taps, nt, PLX_DIAG_VALUE(g_blur_ablate)); break;
     }
 }
 
@@ -401,13 +400,13 @@ __global__ __launch_bounds__(1024) void blur_small_kernel(const float *__restric
 template <class V, int ORDER>   // ORDER 0 = runtime order
 __global__ __launch_bounds__(kBlock) void blur_axis_kernel(const V *__restrict__ old, V *__restrict__ out,
                                                            const int *__restrict__ nbr, int m, int64_t mstride,
-                                                           int rowlen, int order_rt, TapArgs taps, int ntiles, int remap,
+                                                           int rowlen, int order_rt, TapArgs taps, int ntiles,
                                                            int ablate)
 {
     ablate = PLX_DIAG_VALUE(ablate);                   // diagnostics are compiled into libplx_diag.so only
     using O = VecOps<V>;
     const int order = ORDER > 0 ? ORDER : order_rt;
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     // 32-bit index arithmetic: a 64-bit division costs more VALU time than the whole rest of the thread
     // (blur_impl checks m * rowlen < 2^31)
@@ -437,9 +436,9 @@ __global__ __launch_bounds__(kBlock) void blur_axis_kernel(const V *__restrict__
 template <int ORDER, int ROWLEN>
 __global__ __launch_bounds__(kBlock) void blur_axis_narrow_kernel(const float4 *__restrict__ old, float4 *__restrict__ out,
                                                                   const int *__restrict__ nbr, uint32_t total,
-                                                                  uint32_t mstride, TapArgs taps, int ntiles, int remap)
+                                                                  uint32_t mstride, TapArgs taps, int ntiles)
 {
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const uint32_t item = (uint32_t)tile * kBlock + threadIdx.x;
     if (item >= total) return;
@@ -463,16 +462,16 @@ __global__ __launch_bounds__(kBlock) void blur_axis_narrow_kernel(const float4 *
 
 template <int ORDER>
 static void launch_blur_narrow(const float4 *cur, float4 *nxt, const int *nb, int m, int64_t mstride, int rowlen,
-                               const TapArgs &taps, hipStream_t stream, int remap)
+                               const TapArgs &taps, hipStream_t stream)
 {
     const uint32_t total = (uint32_t)m * (uint32_t)rowlen;
     const int nt = ceil_div((int64_t)total, kBlock);
-    const int grid = tile_grid(nt, remap);
+    const int grid = tile_grid(nt);
     switch (rowlen) {
-    case 1: blur_axis_narrow_kernel<ORDER, 1><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt, remap); break;
-    case 2: blur_axis_narrow_kernel<ORDER, 2><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt, remap); break;
-    case 3: blur_axis_narrow_kernel<ORDER, 3><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt, remap); break;
-    default: blur_axis_narrow_kernel<ORDER, 4><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt, remap); break;
+    case 1: blur_axis_narrow_kernel<ORDER, 1><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt); break;
+    case 2: blur_axis_narrow_kernel<ORDER, 2><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt); break;
+    case 3: blur_axis_narrow_kernel<ORDER, 3><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt); break;
+    default: blur_axis_narrow_kernel<ORDER, 4><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, total, (uint32_t)mstride, taps, nt); break;
     }
 }
 
@@ -711,9 +710,9 @@ static void launch_blur_v1(const float *cur, float *nxt, const int *nb, int m, i
 {
     const int nt4 = ceil_div(ceil_div(m, 4), kBlock), nt2 = ceil_div(ceil_div(m, 2), kBlock);
     if (g_blur_vpt == 4)
-        blur_axis_v1_kernel<ORDER, 4><<<tile_grid(nt4, g_xcd_remap), kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, taps, PLX_DIAG_VALUE(g_blur_ablate), nt4, g_xcd_remap);
+        blur_axis_v1_kernel<ORDER, 4><<<tile_grid(nt4), kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, taps, PLX_DIAG_VALUE(g_blur_ablate), nt4);
     else
-        blur_axis_v1_kernel<ORDER, 2><<<tile_grid(nt2, g_xcd_remap), kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, taps, PLX_DIAG_VALUE(g_blur_ablate), nt2, g_xcd_remap);
+        blur_axis_v1_kernel<ORDER, 2><<<tile_grid(nt2), kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, taps, PLX_DIAG_VALUE(g_blur_ablate), nt2);
 }
 
 template <class V>
@@ -721,12 +720,12 @@ static void launch_blur_general(const V *cur, V *nxt, const int *nb, int m, int6
                                 const TapArgs &taps, hipStream_t stream)
 {
     const int nt = ceil_div((int64_t)m * rowlen, kBlock);
-    const int grid = tile_grid(nt, g_xcd_remap);
+    const int grid = tile_grid(nt);
     switch (order) {
-    case 1: blur_axis_kernel<V, 1><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, g_xcd_remap, PLX_DIAG_VALUE(g_blur_ablate)); break;
-    case 2: blur_axis_kernel<V, 2><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, g_xcd_remap, PLX_DIAG_VALUE(g_blur_ablate)); break;
-    case 3: blur_axis_kernel<V, 3><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, g_xcd_remap, PLX_DIAG_VALUE(g_blur_ablate)); break;
-    default: blur_axis_kernel<V, 0><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, g_xcd_remap, PLX_DIAG_VALUE(g_blur_ablate)); break;
+    case 1: blur_axis_kernel<V, 1><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, PLX_DIAG_VALUE(g_blur_ablate)); break;
+    case 2: blur_axis_kernel<V, 2><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, PLX_DIAG_VALUE(g_blur_ablate)); break;
+    case 3: blur_axis_kernel<V, 3><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, PLX_DIAG_VALUE(g_blur_ablate)); break;
+    default: blur_axis_kernel<V, 0><<<grid, kBlock, 0, stream>>>(cur, nxt, nb, m, mstride, rowlen, order, taps, nt, PLX_DIAG_VALUE(g_blur_ablate)); break;
     }
 }
 
@@ -791,7 +790,7 @@ int blur_impl(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *re
         if (pair_vec && pair >= 0) {
             const int *pn = L->pair_nbr.as<int>() + (size_t)pair * 8 * L->mstride;
             launch_blur_pair_narrow(reinterpret_cast<const float4 *>(cur), reinterpret_cast<float4 *>(nxt), pn, m, L->mstride,
-                                    vdp / 4, L->taps, stream, g_xcd_remap);
+                                    vdp / 4, L->taps, stream);
             paired = true;
             ++axis;
             float *t = cur; cur = nxt; nxt = t;
@@ -802,10 +801,10 @@ int blur_impl(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *re
             const int *pn = L->pair_nbr.as<int>() + (size_t)pair * 8 * L->mstride;
             if (g_blur_vpt == 4) {
                 const int nt = ceil_div(ceil_div(m, 4), kBlock);
-                blur_pair_v1_kernel<4><<<tile_grid(nt, g_xcd_remap), kBlock, 0, stream>>>(cur, nxt, pn, m, L->mstride, L->taps, nt, g_xcd_remap);
+                blur_pair_v1_kernel<4><<<tile_grid(nt), kBlock, 0, stream>>>(cur, nxt, pn, m, L->mstride, L->taps, nt);
             } else {
                 const int nt = ceil_div(ceil_div(m, 2), kBlock);
-                blur_pair_v1_kernel<2><<<tile_grid(nt, g_xcd_remap), kBlock, 0, stream>>>(cur, nxt, pn, m, L->mstride, L->taps, nt, g_xcd_remap);
+                blur_pair_v1_kernel<2><<<tile_grid(nt), kBlock, 0, stream>>>(cur, nxt, pn, m, L->mstride, L->taps, nt);
             }
             paired = true;
             ++axis;
@@ -838,9 +837,9 @@ int blur_impl(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *re
             float4 *n4 = reinterpret_cast<float4 *>(nxt);
             // nb is already offset to this axis: plane offsets inside the kernel stay below 2 * order * mstride
             switch (order) {
-            case 1: launch_blur_narrow<1>(c4, n4, nb, m, L->mstride, vdp / 4, L->taps, stream, g_xcd_remap); break;
-            case 2: launch_blur_narrow<2>(c4, n4, nb, m, L->mstride, vdp / 4, L->taps, stream, g_xcd_remap); break;
-            default: launch_blur_narrow<3>(c4, n4, nb, m, L->mstride, vdp / 4, L->taps, stream, g_xcd_remap); break;
+            case 1: launch_blur_narrow<1>(c4, n4, nb, m, L->mstride, vdp / 4, L->taps, stream); break;
+            case 2: launch_blur_narrow<2>(c4, n4, nb, m, L->mstride, vdp / 4, L->taps, stream); break;
+            default: launch_blur_narrow<3>(c4, n4, nb, m, L->mstride, vdp / 4, L->taps, stream); break;
             }
             L->kn_blur = "blur_axis_narrow_kernel";
         } else if (order >= 1 && order <= 3 && g_blur_multi && vdp / 4 >= (g_blur_multi >= 2 ? 32 : 17)) {   // narrower rows: no gain (vd 2..16 measured 0-30 % slower); 17..31 chunks: 5-8 % faster than the general kernel (round 6; blur_multi = 2: the 32-chunk gate of rounds 1-5)

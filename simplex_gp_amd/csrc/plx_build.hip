@@ -226,7 +226,6 @@ int read_back(plx_lattice *L, const int *d_src, int count, int *h_dst, hipStream
     mailbox_kernel<<<1, 64, 0, stream>>>(d_src, count, L->h_mail, seq);
     PLX_HIP_TRY(hipGetLastError());
     volatile int *mail = L->h_mail;
-    if (!g_readback_spin) PLX_HIP_TRY(hipStreamSynchronize(stream));
     const auto t0 = std::chrono::steady_clock::now();
     int spins = 0;
     while (__atomic_load_n(const_cast<int *>(mail), __ATOMIC_ACQUIRE) != seq) {
@@ -256,16 +255,17 @@ __device__ __forceinline__ void elevate(const float (&pos)[D], const ScaleArgs &
 }
 
 // ----------------------------------------------------------------------------
-// order: sort key of a point = (shard, rounded lattice coordinates bit-interleaved along their Z-curve, or
-// lexicographically).  The keys are COMPACT: a first pass finds the range of every rounded coordinate, the host reads
+// order: sort key of a point = (shard, rounded lattice coordinates bit-interleaved along their Z-curve).  The keys are
+// COMPACT: a first pass finds the range of every rounded coordinate, the host reads
 // the 2 (d+1) numbers back through the mailbox (read_back: no stream synchronisation) and gives every coordinate exactly
 // the bits its range needs, so the radix sort runs over the significant bits only (N = 1e6, d = 8, l = 1: 36 bits
 // instead of 63).  Outliers cost bits, never correctness: past 62 key bits the widest coordinates lose low bits.
 
 constexpr int kMaxOrderCoords = 16;
+// the key layout comes from the coordinate ranges of every kOrderSample-th point once there are this many (coord_range_kernel)
+constexpr int kOrderSample = 8, kOrderSampleMinPoints = 1 << 16;
 struct OrderArgs {
     int n_shards, ncoord;            // ncoord = min(d+1, 16) leading coordinates are used
-    int zcurve;                      // g_order_zcurve
     int maxbits;                     // widest coordinate
     long long base, extra;           // shard layout: first `extra` shards have base+1 rows
     int lo[kMaxOrderCoords], bits[kMaxOrderCoords], drop[kMaxOrderCoords];   // per coordinate: smallest value, key bits, low bits dropped
@@ -273,7 +273,7 @@ struct OrderArgs {
 
 // rounded lattice coordinates of a point (the cell of its nearest zero-colour vertex, in units of d+1)
 template <int D>
-__device__ __forceinline__ void order_coords(const float *__restrict__ x, int p, const ScaleArgs &sf, int zcurve, int (&q)[D + 1])
+__device__ __forceinline__ void order_coords(const float *__restrict__ x, int p, const ScaleArgs &sf, int (&q)[D + 1])
 {
     constexpr int D1 = D + 1;
     float pos[D], el[D1];
@@ -286,19 +286,11 @@ __device__ __forceinline__ void order_coords(const float *__restrict__ x, int p,
         c = fminf(fmaxf(c, -1.0e6f), 1.0e6f);                // NaN -> -1e6 (fmaxf), rejected later by embed
         q[i] = (int)c;
     }
-    if (zcurve == 2) {
-        // the vertices' own curve (renumber_vertices): blur-axis coordinates a_i = q_d - q_i, i < d.  A point and the
-        // vertices of its simplex differ by at most one step in every a_i, so points and vertices that meet in splat and
-        // slice are close on the same curve.  Measured against mode 1 (N = 1e6, d = 8): +-3 % per MVM (l = 1.0 93.7 vs
-        // 91.4 us, l = 0.5 299 vs 309, CG iteration 34.8 vs 35.0 ms): not the default.
-#pragma unroll
-        for (int i = 0; i < D; ++i) q[i] = q[D] - q[i];
-    }
 }
 
 // range[2c] = max q_c, range[2c+1] = max -q_c over all points (range[] preset to a very negative number)
 template <int D>
-__global__ __launch_bounds__(kBlock) void coord_range_kernel(const float *__restrict__ x, int n, ScaleArgs sf, int zcurve,
+__global__ __launch_bounds__(kBlock) void coord_range_kernel(const float *__restrict__ x, int n, ScaleArgs sf,
                                                              int ncoord, int *__restrict__ range, int stride)
 {
     constexpr int D1 = D + 1;
@@ -310,7 +302,7 @@ __global__ __launch_bounds__(kBlock) void coord_range_kernel(const float *__rest
     const int p = (int)(pl < n ? pl : n - 1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int q[D1];
-    order_coords<D>(x, min(p, n - 1), sf, zcurve, q);          // a padding thread repeats the last point: no effect on the range
+    order_coords<D>(x, min(p, n - 1), sf, q);          // a padding thread repeats the last point: no effect on the range
 #pragma unroll
     for (int i = 0; i < D1; ++i) {
         if (i < kMaxOrderCoords) {
@@ -370,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void sortkey_kernel(const float *__restrict
     const int p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
     int q[D1];
-    order_coords<D>(x, p, sf, oa.zcurve, q);
+    order_coords<D>(x, p, sf, q);
     const long long split = (oa.base + 1) * oa.extra;
     const unsigned long long shard =
         (oa.n_shards <= 1) ? 0ull
@@ -383,21 +375,15 @@ __global__ __launch_bounds__(kBlock) void sortkey_kernel(const float *__restrict
             const int top = (1 << oa.bits[i]) - 1;
             q[i] = v < 0 ? 0 : (v > top ? top : v);
         }
-    if (oa.zcurve) {
-        // Z-order: bit b of every coordinate (that has one) before bit b-1 of any.  Every blur axis changes all d+1
-        // coordinates, so under the lexicographic order each neighbour is about a slab of the leading
-        // coordinate away (median 13k-320k vertex ids at N = 1e6, d = 8, l = 0.69); along the Z-curve
-        // the medians are 6k-16k and the medium-regime blur is 3-5 % faster (tools/ab_order.py).
-        // Ordering by the blur-axis coordinates q_i - q_d instead was measured too: no gain.
-        for (int b = oa.maxbits - 1; b >= 0; --b)
-#pragma unroll
-            for (int i = 0; i < D1; ++i)
-                if (i < kMaxOrderCoords && i < oa.ncoord && oa.bits[i] > b) key = (key << 1) | (unsigned long long)((q[i] >> b) & 1);
-    } else {
+    // Z-order: bit b of every coordinate (that has one) before bit b-1 of any.  Every blur axis changes all d+1
+    // coordinates, so under a lexicographic order each neighbour is about a slab of the leading
+    // coordinate away (median 13k-320k vertex ids at N = 1e6, d = 8, l = 0.69); along the Z-curve
+    // the medians are 6k-16k and the medium-regime blur is 3-5 % faster.
+    // Ordering by the blur-axis coordinates q_d - q_i instead was measured too: +-3 % per MVM, no gain.
+    for (int b = oa.maxbits - 1; b >= 0; --b)
 #pragma unroll
         for (int i = 0; i < D1; ++i)
-            if (i < kMaxOrderCoords && i < oa.ncoord) key = (key << oa.bits[i]) | (unsigned long long)q[i];
-    }
+            if (i < kMaxOrderCoords && i < oa.ncoord && oa.bits[i] > b) key = (key << 1) | (unsigned long long)((q[i] >> b) & 1);
     keys[p] = key;
     iota[p] = (uint32_t)p;
 }
@@ -449,10 +435,9 @@ template <int D>
 __global__ __launch_bounds__(kBlock) void embed_kernel(const float *__restrict__ x,
                                                        const uint32_t *__restrict__ perm, int n, ScaleArgs sf,
                                                        float *__restrict__ ew, int *__restrict__ counters,
-                                                       uint32_t *__restrict__ prec, int *__restrict__ vrange)
+                                                       uint32_t *__restrict__ prec)
 {
     constexpr int D1 = D + 1;
-    __shared__ int vred[2 * kMaxOrderCoords];
     const bool valid = blockIdx.x * kBlock + threadIdx.x < n;
     const int p = valid ? blockIdx.x * kBlock + threadIdx.x : n - 1;      // (a padding thread repeats the last point and stores nothing)
 
@@ -536,39 +521,6 @@ __global__ __launch_bounds__(kBlock) void embed_kernel(const float *__restrict__
 
     if (bad) atomicOr(&counters[1], 1);
 
-    // Range of the blur-axis coordinates a_c = (k_d - k_c) / (d+1), c < d, over this point's d+1 vertices: what the Morton
-    // renumbering lays its codes out over (renumber_vertices; it used to find it with a pass over the vertex keys and a
-    // read-back of its own).  At corner 0 the canonical offsets vanish, a_c(0) = (gr_d - gr_c) / (d+1); corner r adds
-    // canonical[r][rank_d] - canonical[r][rank_c] = +(d+1) for the corners with rank_d <= d-r < rank_c, -(d+1) for those with
-    // rank_c <= d-r < rank_d (h:364-369): the coordinate runs over [a_c(0), a_c(0) + 1] if rank_c > rank_d, else over
-    // [a_c(0) - 1, a_c(0)].  Workgroup maxima through LDS, then one guarded atomicMax per workgroup and bound.
-    if (vrange) {
-        // thread 0's values seed the workgroup maxima; a thread then adds only what exceeds the word it reads (neighbouring
-        // points of the lattice order differ by a step or two, so a handful of LDS atomics per workgroup remain; 256 threads
-        // adding to the same 32 words one after the other cost 100 us per build)
-        int hi[D < kMaxOrderCoords ? D : kMaxOrderCoords], nlo[D < kMaxOrderCoords ? D : kMaxOrderCoords];
-#pragma unroll
-        for (int c = 0; c < D; ++c)
-            if (c < kMaxOrderCoords) {
-                const int a0 = (gr[D] - gr[c]) / D1;                 // exact: all coordinates of a lattice point agree mod d+1
-                hi[c] = a0 + (rk[c] > rk[D] ? 1 : 0);
-                nlo[c] = -(a0 - (rk[c] < rk[D] ? 1 : 0));
-                if (threadIdx.x == 0) { vred[2 * c] = hi[c]; vred[2 * c + 1] = nlo[c]; }
-            }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < D; ++c)
-            if (c < kMaxOrderCoords) {
-                if (hi[c] > vred[2 * c]) atomicMax(&vred[2 * c], hi[c]);
-                if (nlo[c] > vred[2 * c + 1]) atomicMax(&vred[2 * c + 1], nlo[c]);
-            }
-        __syncthreads();
-        const int nred = 2 * (D < kMaxOrderCoords ? D : kMaxOrderCoords);
-        if ((int)threadIdx.x < nred) {
-            const int v = vred[threadIdx.x];
-            if (v > __hip_atomic_load(&vrange[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&vrange[threadIdx.x], v);
-        }
-    }
     if (!valid) return;
 
     // the point record: greedy (first d coordinates) + the final ranks, one byte per coordinate
@@ -661,7 +613,7 @@ template <int D>
 __global__ __launch_bounds__(kBlock) void insert_point_kernel(const uint32_t *__restrict__ prec, int n,
                                                               uint32_t *__restrict__ table, HashSel hs,
                                                               uint32_t *__restrict__ eslot, int dedupe,
-                                                              uint32_t *__restrict__ disp, int ntiles, int remap)
+                                                              uint32_t *__restrict__ disp, int ntiles)
 {
     constexpr int D1 = D + 1;
     constexpr int DW = (D + 1) / 2;
@@ -669,12 +621,12 @@ __global__ __launch_bounds__(kBlock) void insert_point_kernel(const uint32_t *__
     __shared__ uint32_t q_pbase[kInsertQueue], q_h[kInsertQueue], q_who[kInsertQueue];      // who = corner r | leader lane << 8
     __shared__ unsigned long long q_peers[kInsertQueue];                                    // lanes of the wave holding this key
     __shared__ int q_count;
-    // XCD-aware tile order (tile_index; plx_tune insert_xcd bit 0, off): every XCD inserts one contiguous eighth of the
-    // lattice-ordered points, so that the ~22 corners sharing a vertex meet its table line in ONE L2.  Measured SLOWER
+    // Plain tile order.  The XCD-aware order (tile_index with remap: every XCD inserts one contiguous eighth of the
+    // lattice-ordered points, so that the ~22 corners sharing a vertex meet its table line in ONE L2) measured SLOWER
     // (N = 1e6, l = 1: 183 -> 231 us): eight ranges running side by side claim their shared vertices out of index order
     // and lower them afterwards, and the in-order sweep loses the "smaller index already in place" fast path it lives on.
-    // The id lookup (bit 1, on) has no such order to lose: 39 -> 34 us.
-    const int tile = tile_index(ntiles, remap);
+    // The id lookup (ids_kernel, remapped) has no such order to lose: 39 -> 34 us.
+    const int tile = tile_index(ntiles, 0);
     if (tile < 0) return;
     if (threadIdx.x == 0) q_count = 0;
     __syncthreads();
@@ -998,9 +950,9 @@ __global__ __launch_bounds__(kBlock) void assign_kernel(const uint32_t *__restri
 
 __global__ __launch_bounds__(kBlock) void ids_kernel(const uint32_t *__restrict__ eslot,
                                                      const uint32_t *__restrict__ table, int n,
-                                                     int *__restrict__ evid, uint32_t idmask, int ntiles, int remap)
+                                                     int *__restrict__ evid, uint32_t idmask, int ntiles)
 {
-    const int tile = tile_index(ntiles, remap);      // (XCD-aware: the table lines of a vertex are read by one L2)
+    const int tile = tile_index(ntiles);      // (XCD-aware: the table lines of a vertex are read by one L2)
     if (tile < 0) return;
     const int p = tile * kBlock + threadIdx.x;
     if (p >= n) return;
@@ -1087,8 +1039,8 @@ __global__ __launch_bounds__(kBlock) void nbr_rows_init_kernel(const uint32_t *_
 // neighbours: h:539-545 evaluated once per lattice instead of once per MVM.
 // nbr[(axis*2r + s)*mstride + i]; s enumerates nid = -r..-1, 1..r.
 
-// SYMMETRIC = true: only the positive taps are looked up; a hit j = nbr(i, +t) also fills
-// nbr(j, -t) = i (the relation is symmetric), the planes having been preset to -1.
+// Only the positive taps are looked up; a hit j = nbr(i, +t) also fills nbr(j, -t) = i (the relation is symmetric),
+// the planes having been preset to -1 (fine regime 7.2 -> 4.9 ms against looking up all 2r taps).
 // One bit per hash slot: occupied.  On large, sparse lattices most neighbour lookups are for vertices that do not
 // exist (88 % at l = 0.25, 43 % at l = 0.69: SURVEY 6.3), and an absent key ends its probe sequence at the first empty
 // slot: with the bit tested first that slot is never fetched -- a random 4-byte read of a 134 MB table becomes a read of
@@ -1114,18 +1066,19 @@ __global__ __launch_bounds__(kBlock) void slotmap_kernel(const uint32_t *__restr
 // position: no key compare, no table) or PROVEN absent.  Only targets outside the window (and axis d, which moves every
 // coordinate) go to the hash table.  Where the bits of (coordinate c, bit b) sit in a code, and each coordinate's
 // measured range, come from the layout the renumbering used.
+constexpr int kNbrWindow = 512;   // sorted codes searched on either side of the vertex
 struct NbrCode {
     int nbits[kMaxOrderCoords], lo[kMaxOrderCoords], hi[kMaxOrderCoords];
     unsigned char pos[kMaxOrderCoords][16];
 };
 
-template <int D, bool SYMMETRIC>
+template <int D>
 __global__ __launch_bounds__(kBlock) void neighbor_kernel(const uint32_t *__restrict__ vkeys, int m,
                                                           int64_t mstride, int order,
                                                           const uint32_t *__restrict__ table,
                                                           HashSel hs, uint32_t idmask, int *__restrict__ nbr, int plane_fast,
                                                           const uint32_t *__restrict__ slotmap,
-                                                          const unsigned long long *__restrict__ vcode, NbrCode nc, int window)
+                                                          const unsigned long long *__restrict__ vcode, NbrCode nc)
 {
     const uint32_t mask = hs.mask;
     constexpr int D1 = D + 1;
@@ -1153,7 +1106,7 @@ __global__ __launch_bounds__(kBlock) void neighbor_kernel(const uint32_t *__rest
     }
 
     int *plane = nbr + (size_t)axis * 2 * order * mstride;
-    for (int s = SYMMETRIC ? order : 0; s < 2 * order; ++s) {
+    for (int s = order; s < 2 * order; ++s) {
         const int nid = (s < order) ? (s - order) : (s - order + 1);
         if (windowed) {
             const int ajn = aj - nid;
@@ -1168,8 +1121,8 @@ __global__ __launch_bounds__(kBlock) void neighbor_kernel(const uint32_t *__rest
                     const int pb = nc.pos[axis][b];
                     T = (T & ~(1ull << pb)) | ((unsigned long long)((q >> b) & 1) << pb);
                 }
-                const int lo_i = T < ci ? max(0, i - window) : i + 1;
-                const int hi_i = T < ci ? i : min(m, i + 1 + window);
+                const int lo_i = T < ci ? max(0, i - kNbrWindow) : i + 1;
+                const int hi_i = T < ci ? i : min(m, i + 1 + kNbrWindow);
                 if (lo_i < hi_i && vcode[lo_i] <= T && T <= vcode[hi_i - 1]) {
                     int a = lo_i, e = hi_i;
                     while (a < e) {
@@ -1182,7 +1135,7 @@ __global__ __launch_bounds__(kBlock) void neighbor_kernel(const uint32_t *__rest
             }
             if (resolved) {
                 plane[(size_t)s * mstride + i] = found_w;
-                if (SYMMETRIC && found_w >= 0) plane[(size_t)(order - nid) * mstride + found_w] = i;
+                if (found_w >= 0) plane[(size_t)(order - nid) * mstride + found_w] = i;
                 continue;
             }
         }
@@ -1212,7 +1165,7 @@ __global__ __launch_bounds__(kBlock) void neighbor_kernel(const uint32_t *__rest
             }
         }
         plane[(size_t)s * mstride + i] = found;
-        if (SYMMETRIC && found >= 0) plane[(size_t)(order - nid) * mstride + found] = i;   // slot of tap -nid
+        if (found >= 0) plane[(size_t)(order - nid) * mstride + found] = i;   // slot of tap -nid
     }
 }
 
@@ -1220,7 +1173,7 @@ __global__ __launch_bounds__(kBlock) void neighbor_kernel(const uint32_t *__rest
 // ----------------------------------------------------------------------------
 // XCD-sliced neighbour lookups (round 5; hash_v = 2).  Where most neighbours do not exist (88 % at l = 0.25) a lookup is a
 // proof of absence, and every random 4-byte read of the 134 MB table, of its 4 MB occupancy bitmap or of a 16-byte key costs
-// a 128-byte line fill: neighbor_kernel<8, true> moved 15.6 GB to write a 643 MB table (profiles/r04_summary.md), at the
+// a 128-byte line fill: neighbor_kernel<8> moved 15.6 GB to write a 643 MB table (profiles/r04_summary.md), at the
 // line-fill bandwidth of the fabric.  Here the probing runs on a MAP of four bits per slot -- 0 = empty, else 1 +
 // fingerprint % 15 -- and every lookup is served by the XCD that owns the slot's eighth of that map: workgroup b serves
 // slice b % 8 of vertex tile b / 8 (workgroups b and b + 8 share an XCD, MI355X_MICROARCH.md "Workgroup dispatch"), so an
@@ -1229,7 +1182,7 @@ __global__ __launch_bounds__(kBlock) void neighbor_kernel(const uint32_t *__rest
 // pre-mix hash is the vertex's own plus a constant per (axis, tap), and the owning slice is the top 3 bits of one product.
 // The table and a key are touched only when a nibble matches the lookup's own (the neighbour exists, or 1 in 15 of the
 // occupied slots met on the way).  Placement is a speed assumption only: each (tile, slice) pair is one workgroup wherever
-// it runs.  Positive taps only, hits mirrored (the SYMMETRIC form of neighbor_kernel); same table, bit for bit.
+// it runs.  Positive taps only, hits mirrored (as in neighbor_kernel); same table, bit for bit.
 __global__ __launch_bounds__(kBlock) void nibmap_kernel(const uint32_t *__restrict__ table, uint64_t nwords, int fp_on,
                                                         uint32_t *__restrict__ nib)
 {
@@ -1744,7 +1697,7 @@ static bool will_renumber(const plx_lattice *L, int64_t m, int64_t corners)
 }
 
 template <int D>
-static int renumber_vertices(plx_lattice *L, int64_t corners, hipStream_t stream, const int *h_range_known = nullptr)
+static int renumber_vertices(plx_lattice *L, int64_t corners, hipStream_t stream)
 {
     // corners: how many (point, vertex) incidences stand behind the m vertices -- n (d+1) of the whole job, or the sum of
     // the per-rank vertex counts when only those are known (plx_build_merge); the same number on every rank
@@ -1767,15 +1720,10 @@ static int renumber_vertices(plx_lattice *L, int64_t corners, hipStream_t stream
     const int nb = ceil_div(m, kBlock);
     // range of every blur-axis coordinate -> exactly the code bits it needs (counters[32 ..] preset to a very negative int)
     int h_range[2 * kMaxOrderCoords];
-    if (h_range_known) {
-        // (the embedding already found the range of every blur-axis coordinate: it came back with m)
-        memcpy(h_range, h_range_known, sizeof(h_range));
-    } else {
-        int *range = L->counters.as<int>() + 32;
-        PLX_HIP_TRY(hipMemsetAsync(range, 0x80, 2 * kMaxOrderCoords * sizeof(int), stream));
-        vertex_range_kernel<D><<<nb, kBlock, 0, stream>>>(L->vkeys.as<uint32_t>(), m, ca.ncoord, range);
-        PLX_TRY(read_back(L, range, 2 * ca.ncoord, h_range, stream));
-    }
+    int *range = L->counters.as<int>() + 32;
+    PLX_HIP_TRY(hipMemsetAsync(range, 0x80, 2 * kMaxOrderCoords * sizeof(int), stream));
+    vertex_range_kernel<D><<<nb, kBlock, 0, stream>>>(L->vkeys.as<uint32_t>(), m, ca.ncoord, range);
+    PLX_TRY(read_back(L, range, 2 * ca.ncoord, h_range, stream));
     const int key_bits = layout_key_bits(h_range, ca.ncoord, 0, ca.lo, ca.bits, ca.drop, &ca.maxbits);
     vertex_code_kernel<D><<<nb, kBlock, 0, stream>>>(L->vkeys.as<uint32_t>(), m, ca, L->sortkey_in.as<unsigned long long>(),
                                                      L->iota.as<uint32_t>());
@@ -1866,9 +1814,7 @@ static int stage_local(plx_lattice *L, const float *d_ref, hipStream_t stream, i
     OrderArgs oa;
     memset(&oa, 0, sizeof(oa));
     oa.n_shards = L->n_shards;
-    oa.zcurve = g_order_zcurve;
     oa.ncoord = D1 < kMaxOrderCoords ? D1 : kMaxOrderCoords;
-    if (oa.zcurve == 2) oa.ncoord = D < kMaxOrderCoords ? D : kMaxOrderCoords;
     int shard_bits = 0;
     while ((1 << shard_bits) < L->n_shards) ++shard_bits;
     oa.base = L->n / L->n_shards;
@@ -1903,24 +1849,14 @@ static int stage_local(plx_lattice *L, const float *d_ref, hipStream_t stream, i
     if (keep_order) {
         ++L->order_age;
     } else if (g_sort_points) {
-        int key_bits;
-        if (g_order_compact) {
-            // range of every rounded coordinate -> exactly the key bits it needs (counters[32 ..] preset to a very negative int)
-            int *range = L->counters.as<int>() + 32;
-            PLX_HIP_TRY(hipMemsetAsync(range, 0x80, 2 * kMaxOrderCoords * sizeof(int), stream));
-            const int rstride = (g_order_sample > 1 && n >= (1 << 16)) ? g_order_sample : 1;
-            coord_range_kernel<D><<<ceil_div(ceil_div(n, rstride), kBlock), kBlock, 0, stream>>>(d_ref, n, sf, oa.zcurve, oa.ncoord, range,
-                                                                                                 rstride);
-            int h_range[2 * kMaxOrderCoords];
-            PLX_TRY(read_back(L, range, 2 * oa.ncoord, h_range, stream));
-            key_bits = shard_bits + layout_key_bits(h_range, oa.ncoord, shard_bits, oa.lo, oa.bits, oa.drop, &oa.maxbits);
-        } else {
-            int b = (64 - shard_bits) / oa.ncoord;
-            if (b > 8) b = 8;
-            for (int c = 0; c < oa.ncoord; ++c) { oa.lo[c] = -(1 << (b - 1)); oa.bits[c] = b; oa.drop[c] = 0; }
-            oa.maxbits = b;
-            key_bits = shard_bits + b * oa.ncoord;
-        }
+        // range of every rounded coordinate -> exactly the key bits it needs (counters[32 ..] preset to a very negative int)
+        int *range = L->counters.as<int>() + 32;
+        PLX_HIP_TRY(hipMemsetAsync(range, 0x80, 2 * kMaxOrderCoords * sizeof(int), stream));
+        const int rstride = n >= kOrderSampleMinPoints ? kOrderSample : 1;
+        coord_range_kernel<D><<<ceil_div(ceil_div(n, rstride), kBlock), kBlock, 0, stream>>>(d_ref, n, sf, oa.ncoord, range, rstride);
+        int h_range[2 * kMaxOrderCoords];
+        PLX_TRY(read_back(L, range, 2 * oa.ncoord, h_range, stream));
+        const int key_bits = shard_bits + layout_key_bits(h_range, oa.ncoord, shard_bits, oa.lo, oa.bits, oa.drop, &oa.maxbits);
         sortkey_kernel<D><<<nblocks, kBlock, 0, stream>>>(d_ref, n, sf, oa, L->sortkey_in.as<unsigned long long>(),
                                                           L->iota.as<uint32_t>());
         int second = 0;
@@ -1932,21 +1868,19 @@ static int stage_local(plx_lattice *L, const float *d_ref, hipStream_t stream, i
         iota_kernel<<<nblocks, kBlock, 0, stream>>>(L->perm.as<uint32_t>(), n);
         L->order_n = 0;
     }
-    // counters[30] = m, [31] = key-range error flag, [32 .. 63] = range of the vertices' blur-axis coordinates: one read-back
+    // counters[30] = m, [31] = key-range error flag: one read-back
     int *cnt = L->counters.as<int>() + 30;
-    const bool embed_range = g_embed_vrange != 0 && !L->for_merge && g_vertex_order != 0;
-    if (embed_range) PLX_HIP_TRY(hipMemsetAsync(cnt + 2, 0x80, 2 * kMaxOrderCoords * sizeof(int), stream));
     embed_kernel<D><<<nblocks, kBlock, 0, stream>>>(d_ref, L->perm.as<uint32_t>(), n, sf, L->ew.as<float>(), cnt,
-                                                    L->prank.as<uint32_t>(), embed_range ? cnt + 2 : nullptr);
+                                                    L->prank.as<uint32_t>());
     mark();
     // flag_own: the insert marks owners (bit 31 of eslot: the table must not need that bit) and displaced corners (flagmask
     // doubles as the displaced mask until flag_own_kernel turns it into the first-touch mask in place); a table of 2^32
     // slots (more than 2^30 corners) has no bit to spare and takes the table-gather form (flag_kernel)
     const bool flag_own = L->table_bits <= 31;
     if (flag_own) PLX_HIP_TRY(hipMemsetAsync(L->flagmask.p, 0, (size_t)n * 8, stream));
-    insert_point_kernel<D><<<tile_grid(nblocks, g_insert_xcd & 1), kBlock, 0, stream>>>(
+    insert_point_kernel<D><<<nblocks, kBlock, 0, stream>>>(
         L->prank.as<uint32_t>(), n, L->table.as<uint32_t>(), hash_sel(L), L->eslot.as<uint32_t>(), g_insert_dedupe,
-        flag_own ? L->flagmask.as<uint32_t>() : nullptr, nblocks, g_insert_xcd & 1);
+        flag_own ? L->flagmask.as<uint32_t>() : nullptr, nblocks);
     mark();
     L->flags_valid = !L->for_merge;      // the first-touch bits of this build's points stay in flagmask (plx_first.hip reads them)
     if (flag_own)
@@ -1956,8 +1890,8 @@ static int stage_local(plx_lattice *L, const float *d_ref, hipStream_t stream, i
         flag_kernel<D1><<<nblocks, kBlock, 0, stream>>>(L->eslot.as<uint32_t>(), L->table.as<uint32_t>(), n,
                                                         L->flagmask.as<uint32_t>(), L->blockcnt.as<int>());
     scan_blocks_kernel<<<1, kWideScanT, 0, stream>>>(L->blockcnt.as<int>(), nblocks, cnt);
-    int h_cnt[2 + 2 * kMaxOrderCoords];
-    PLX_TRY(read_back(L, cnt, embed_range ? 2 + 2 * kMaxOrderCoords : 2, h_cnt, stream));   // m sizes everything below
+    int h_cnt[2];
+    PLX_TRY(read_back(L, cnt, 2, h_cnt, stream));   // m sizes everything below
     if (h_cnt[1] != 0) {
         set_error("a lattice coordinate left the int16 key range (|x/lengthscale| too large, NaN or Inf)");
         return PLX_ERR_KEY_RANGE;
@@ -1979,15 +1913,14 @@ static int stage_local(plx_lattice *L, const float *d_ref, hipStream_t stream, i
                                                      assign_evid ? L->evid.as<int>() : nullptr,
                                                      (L->vs0_valid && ids_final) ? L->vs0.as<uint32_t>() : nullptr,
                                                      (want_rank && ids_final) ? L->vowner.as<uint32_t>() : nullptr);
-    if (!L->for_merge) PLX_TRY(renumber_vertices<D>(L, E, stream, embed_range ? h_cnt + 2 : nullptr));   // (a job built from local rows renumbers the union, after the merge)
+    if (!L->for_merge) PLX_TRY(renumber_vertices<D>(L, E, stream));   // (a job built from local rows renumbers the union, after the merge)
     mark();
     if (assign_evid)
         ids_rest_kernel<<<nblocks, kBlock, 0, stream>>>(L->eslot.as<uint32_t>(), L->flagmask.as<uint32_t>(), L->table.as<uint32_t>(), n, D1,
                                                         L->evid.as<int>(), L->table_idmask);
     else
-        ids_kernel<<<dim3(tile_grid(nblocks, g_insert_xcd >> 1), D1), kBlock, 0, stream>>>(L->eslot.as<uint32_t>(), L->table.as<uint32_t>(), n,
-                                                                                           L->evid.as<int>(), L->table_idmask, nblocks,
-                                                                                           g_insert_xcd >> 1);
+        ids_kernel<<<dim3(tile_grid(nblocks), D1), kBlock, 0, stream>>>(L->eslot.as<uint32_t>(), L->table.as<uint32_t>(), n,
+                                                                        L->evid.as<int>(), L->table_idmask, nblocks);
     L->prank_valid = want_rank && !L->for_merge;
     mark();
     PLX_HIP_TRY(hipGetLastError());
@@ -2185,21 +2118,21 @@ static int stage_tables(plx_lattice *L, hipStream_t stream, int *evi)
     PLX_TRY(ensure(L->nbr, (size_t)D1 * 2 * order * L->mstride * 4 + 4));
 
     if (order > 0) {
-        const int nplane_fast = (g_insert_plane_fast != 0 && ceil_div(m, kBlock) <= 65535) ? 1 : 0;
+        const int nplane_fast = ceil_div(m, kBlock) <= 65535 ? 1 : 0;      // (grid.y cannot hold more: plane-major above)
         dim3 ngrid(ceil_div(m, kBlock), D1);
         if (nplane_fast) ngrid = dim3(D1, ceil_div(m, kBlock));
         // Morton-numbered lattices: most lookups are decided by a binary search in a window of the sorted codes
         NbrCode nc;
         memset(&nc, 0, sizeof(nc));
         const unsigned long long *vcode = nullptr;
-        if (g_nbr_window > 0 && L->vertex_order == 1 && L->vcode && L->vcode_exact) {
+        if (L->vertex_order == 1 && L->vcode && L->vcode_exact) {
             vcode = L->vcode;
             for (int c = 0; c < kMaxOrderCoords; ++c) {
                 nc.nbits[c] = L->vcode_bits[c]; nc.lo[c] = L->vcode_lo[c]; nc.hi[c] = L->vcode_hi[c];
                 memcpy(nc.pos[c], L->vcode_pos[c], 16);
             }
         }
-        const bool sliced = L->vs0_valid && g_nbr_symmetric && ceil_div(m, kBlock) < (1 << 28) &&
+        const bool sliced = L->vs0_valid && ceil_div(m, kBlock) < (1 << 28) &&
                             (g_nbr_sliced == 2 || (g_nbr_sliced == 1 && vcode == nullptr && m >= (1 << 20)));
         const uint32_t *slotmap = nullptr;
         if (!sliced && (g_nbr_bitmap == 2 || (g_nbr_bitmap == 1 && m >= (1 << 22)))) {
@@ -2235,15 +2168,11 @@ static int stage_tables(plx_lattice *L, hipStream_t stream, int *evi)
             neighbor_sliced_kernel<D><<<8u * (unsigned)ceil_div(m, kBlock * sliced_vpt(D1)), kBlock, 0, stream>>>(
                 L->vs0.as<uint32_t>(), L->vkeys.as<uint32_t>(), m, L->mstride, order, L->table.as<uint32_t>(), hash_sel(L),
                 L->table_idmask, fp_on, L->nibmap.as<uint32_t>(), nd, L->nbr.as<int>(), vaxis);
-        } else if (g_nbr_symmetric) {
-            PLX_HIP_TRY(hipMemsetAsync(L->nbr.p, 0xFF, (size_t)D1 * 2 * order * L->mstride * 4, stream));
-            neighbor_kernel<D, true><<<ngrid, kBlock, 0, stream>>>(L->vkeys.as<uint32_t>(), m, L->mstride, order,
-                                                                    L->table.as<uint32_t>(), hash_sel(L), L->table_idmask,
-                                                                    L->nbr.as<int>(), nplane_fast, slotmap, vcode, nc, g_nbr_window);
         } else {
-            neighbor_kernel<D, false><<<ngrid, kBlock, 0, stream>>>(L->vkeys.as<uint32_t>(), m, L->mstride, order,
-                                                                     L->table.as<uint32_t>(), hash_sel(L), L->table_idmask,
-                                                                     L->nbr.as<int>(), nplane_fast, slotmap, vcode, nc, g_nbr_window);
+            PLX_HIP_TRY(hipMemsetAsync(L->nbr.p, 0xFF, (size_t)D1 * 2 * order * L->mstride * 4, stream));
+            neighbor_kernel<D><<<ngrid, kBlock, 0, stream>>>(L->vkeys.as<uint32_t>(), m, L->mstride, order,
+                                                             L->table.as<uint32_t>(), hash_sel(L), L->table_idmask,
+                                                             L->nbr.as<int>(), nplane_fast, slotmap, vcode, nc);
         }
         L->vcode = nullptr;                                       // (the sort buffers are free for their next user)
     }

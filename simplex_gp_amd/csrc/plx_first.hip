@@ -121,9 +121,9 @@ template <int D1>
 __global__ __launch_bounds__(kBlock) void splat_first_kernel(const uint32_t *__restrict__ flagmask, const int *__restrict__ evid,
                                                              const float *__restrict__ ew, const uint32_t *__restrict__ perm,
                                                              const float *__restrict__ src, int n, float *__restrict__ values,
-                                                             int ntiles, int remap)
+                                                             int ntiles)
 {
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int p = tile * kBlock + threadIdx.x;
     if (p >= n) return;
@@ -148,12 +148,12 @@ template <int D1>
 __global__ __launch_bounds__(kBlock) void splat_first_seq_kernel(const uint32_t *__restrict__ flagmask, const int *__restrict__ evid,
                                                                  const float *__restrict__ ew, const uint32_t *__restrict__ perm,
                                                                  const float *__restrict__ src, int n, float *__restrict__ values,
-                                                                 int ntiles, int remap)
+                                                                 int ntiles)
 {
     __shared__ float prod[kBlock * D1];
     __shared__ int wsum[kBlock / 64];
     __shared__ int s_base;
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int p = tile * kBlock + threadIdx.x;
     const bool live = p < n;
@@ -279,13 +279,13 @@ int splat_first_impl(plx_lattice *L, const float *d_src, float *d_values, hipStr
     const int n = (int)L->n;
     const uint32_t *perm = L->lattice_rows ? nullptr : L->perm.as<uint32_t>();
     const int nt = ceil_div(n, kBlock);
-    const int grid = tile_grid(nt, g_xcd_remap);
+    const int grid = tile_grid(nt);
     const bool seq = L->vertex_order == 0 && g_splat_first != 3;      // first-touch numbering: contiguous id ranges (3: A/B switch)
     switch (L->d + 1) {
 #define PLX_CASE(D1) \
     case D1: \
-        if (seq) splat_first_seq_kernel<D1><<<grid, kBlock, 0, stream>>>(L->flagmask.as<uint32_t>(), L->evid.as<int>(), splat_weights(L), perm, d_src, n, d_values, nt, g_xcd_remap); \
-        else splat_first_kernel<D1><<<grid, kBlock, 0, stream>>>(L->flagmask.as<uint32_t>(), L->evid.as<int>(), splat_weights(L), perm, d_src, n, d_values, nt, g_xcd_remap); \
+        if (seq) splat_first_seq_kernel<D1><<<grid, kBlock, 0, stream>>>(L->flagmask.as<uint32_t>(), L->evid.as<int>(), splat_weights(L), perm, d_src, n, d_values, nt); \
+        else splat_first_kernel<D1><<<grid, kBlock, 0, stream>>>(L->flagmask.as<uint32_t>(), L->evid.as<int>(), splat_weights(L), perm, d_src, n, d_values, nt); \
         break;
         PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9)
         PLX_CASE(10) PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17)

@@ -48,17 +48,11 @@ struct TapArgs { float c[2 * PLX_MAX_ORDER + 1]; };      // blur weights, h:546
 // snapshot (tl_tune), so a plx_tune call never changes what a built lattice does -- it takes effect at the next build.
 struct Tune {
     int sort_points = 1;   // 0 keeps the caller's point order (A/B only)
-    int readback_spin = 1;   // read_back: 1 = spin on the mailbox word, 0 = wait for the stream
-    int order_compact = 1;   // 1: point-order keys over exactly the bits every coordinate's range needs; 0: a fixed 7 / 8 bits per coordinate
-    int order_zcurve = 1;   // 1: points along the Z-curve of their rounded lattice coordinates; 0: lexicographically; 2: Z-curve of the blur-axis coordinates
-    int nbr_symmetric = 1;   // neighbour build looks up the positive taps only and mirrors the hits (fine regime 7.2 -> 4.9 ms)
     int insert_dedupe = 2;   // hashed insert: 2 = every key of a wave probes once, 1 = runs of equal neighbouring lanes probe once, 0 = every lane probes
     int compact_nbr = 1;   // 0 never, 1 when under a quarter of the neighbour slots exist, 2 always
-    int insert_plane_fast = 1;   // the d+1 corner planes of a run of points are adjacent workgroups of the hashed insert / neighbour lookups
     int vertex_order = 1;   // 0: first touch; 1: Morton order where it pays; 2: always
     int blur_vpt = 4;   // vertices per thread in the vd = 1 blur (2 or 4)
     int blur_small = 1;   // all blur passes in one workgroup when m <= 16384 (vd = 1)
-    int xcd_remap = 1;   // workgroup b works on tile (b % 8) * ceil(nb/8) + b / 8: every XCD owns one contiguous slice of the lattice
     int splat_direct = 1;   // vd = 1 CSR splat gathers from d_src through caller-row indices: 0 never, 1 for <= 2e6 corners, 2 always
     int blur_narrow = 1;   // vd 2..16 blur: row length compiled in, branch-free
     int blur_multi = 1;   // vd > 1 blur: 4 items per thread (and, on sparse lattices, only the rows that change) on rows of >= 17 chunks; 2: >= 32 (rounds 1-5)
@@ -67,19 +61,13 @@ struct Tune {
     int blur_fuse = 1;   // two blur axes per launch (vd = 1): 0 never, 1 on cache-resident lattices, 2 always
     int blur_fuse_vec = 1;   // two blur axes per launch for rows of 2..4 chunks
     int block_path = 1;   // 0 never, 1 when the lattice qualifies (see build_blocks), 2 whenever representable
-    int scatter_store = 0;   // slice's row-scattered output stores: 0 plain, 1 non-temporal, 2 agent-scope
     int unpermute_gather = 1;   // caller row order out of slice: 1 = lattice-ordered scratch + a gather pass, 0 = scatter from the slice kernel
     int block_e = 0;   // corners per thread of the block kernels: 0 = per lattice (choose_block_e), 16 or 24
     int block_dense_combine = 1;   // combine numbers the vertices by counting row ends when every vertex has block rows
     int perm_rows = 1;   // multi-column row permutations: 1 = 16-byte chunks in, LDS-transposed whole-line stores out; 0 = the round-3 per-float / per-chunk kernels
-    int nbr_window = 512;   // Morton-numbered lattices: neighbour lookups first search this many sorted codes next to the vertex (0 = hash only)
     int nbr_bitmap = 1;   // neighbour lookups test a slot-occupancy bitmap before they touch the hash table: 0 never, 1 when m >= 2^22, 2 always
     int nbr_sliced = 1;   // neighbour lookups served by the XCD that owns the slot's eighth of a 4-bit-per-slot map (L2 resident): 0 never, 1 when the lattice keeps first-touch numbering and m >= 2^20, 2 always
-    int insert_xcd = 2;   // XCD-aware tile order (each XCD one contiguous eighth of the points): bit 0 the point-per-thread insert (measured slower), bit 1 the id lookup
-    int order_sample = 8;   // point-order key layout from the coordinate ranges of every k-th point (1: of all points); from 65,536 points up
-    int embed_vrange = 0;   // 1: the embedding finds the range of the vertices' blur-axis coordinates (Morton renumbering) itself -- no pass over the vertex keys, no read-back of its own; measured: saves 22 us there, costs the embedding 30 (l = 1) to 70 us (l = 0.25): off
     int reference_growth = 0;   // 1: replay the reference CPU path's hash-table-growth quirk (plx_replay.hip): literal parity with cpp/permutohedral.h where its table doubles; plain single-process builds only, O(m) host work per build (the event form); 2: the lookup-by-lookup form, O(N (d+1)) (the checker of 1)
-    int blk_sort = 15;   // per-block LDS sort of the block tables: 0 = (vertex, corner) pairs, 4 bits per pass; 4 / 5 / 6 = corner index packed under the vertex id, keys only, that many bits per pass, 256 threads; 15 = 5 bits with 512 threads
     int assign_evid = 1;   // the numbering pass stores the vertex id of every first-touch corner itself when the numbering is final; the id lookup then serves the other corners only
     int nbr_seed = 1;   // sliced neighbour lookups: the +1 neighbour that is a corner of the vertex's own first-touch simplex comes from the embedding, no lookup
     int blur_active = 1;   // wide rows on sparse lattices (centre tap 1): a blur pass touches only the vertices that have a neighbour on its axis, in place (0 never, 1 when under kActiveShare of the vertices are, 2 whenever representable)
@@ -98,17 +86,11 @@ extern thread_local const Tune *tl_tune;   // the snapshot of the lattice this t
 
 // the names the kernel files use for the switches
 #define g_sort_points (plx::tl_tune->sort_points)
-#define g_readback_spin (plx::tl_tune->readback_spin)
-#define g_order_compact (plx::tl_tune->order_compact)
-#define g_order_zcurve (plx::tl_tune->order_zcurve)
-#define g_nbr_symmetric (plx::tl_tune->nbr_symmetric)
 #define g_insert_dedupe (plx::tl_tune->insert_dedupe)
 #define g_compact_nbr (plx::tl_tune->compact_nbr)
-#define g_insert_plane_fast (plx::tl_tune->insert_plane_fast)
 #define g_vertex_order (plx::tl_tune->vertex_order)
 #define g_blur_vpt (plx::tl_tune->blur_vpt)
 #define g_blur_small (plx::tl_tune->blur_small)
-#define g_xcd_remap (plx::tl_tune->xcd_remap)
 #define g_splat_direct (plx::tl_tune->splat_direct)
 #define g_blur_narrow (plx::tl_tune->blur_narrow)
 #define g_blur_multi (plx::tl_tune->blur_multi)
@@ -117,19 +99,13 @@ extern thread_local const Tune *tl_tune;   // the snapshot of the lattice this t
 #define g_blur_fuse (plx::tl_tune->blur_fuse)
 #define g_blur_fuse_vec (plx::tl_tune->blur_fuse_vec)
 #define g_block_path (plx::tl_tune->block_path)
-#define g_scatter_store (plx::tl_tune->scatter_store)
 #define g_unpermute_gather (plx::tl_tune->unpermute_gather)
 #define g_block_e (plx::tl_tune->block_e)
 #define g_block_dense_combine (plx::tl_tune->block_dense_combine)
 #define g_nbr_bitmap (plx::tl_tune->nbr_bitmap)
-#define g_nbr_window (plx::tl_tune->nbr_window)
 #define g_perm_rows (plx::tl_tune->perm_rows)
 #define g_splat_first (plx::tl_tune->splat_first)
-#define g_insert_xcd (plx::tl_tune->insert_xcd)
-#define g_order_sample (plx::tl_tune->order_sample)
-#define g_embed_vrange (plx::tl_tune->embed_vrange)
 #define g_reference_growth (plx::tl_tune->reference_growth)
-#define g_blk_sort (plx::tl_tune->blk_sort)
 #define g_assign_evid (plx::tl_tune->assign_evid)
 #define g_nbr_seed (plx::tl_tune->nbr_seed)
 #define g_nbr_sliced (plx::tl_tune->nbr_sliced)

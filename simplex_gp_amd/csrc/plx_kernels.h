@@ -36,12 +36,13 @@ namespace plx {
 
 // kernel-variant switches (plx_tune); defined in plx_tune.hip and plx_build.hip
 
-// Tile index for workgroup blockIdx.x.  With remap the launch has 8 * ceil(ntiles / 8) workgroups and
+// Tile index for workgroup blockIdx.x.  With remap (every kernel but the two that measured faster in plain order and
+// say so) the launch has 8 * ceil(ntiles / 8) workgroups and
 // workgroup b takes tile (b % 8) * per + b / 8: workgroups are dealt to the 8 XCDs round-robin
 // (MI355X_MICROARCH.md, Workgroup dispatch), so every XCD sweeps one contiguous eighth of the tiles and its
 // gathers -- which follow the lattice order -- stay inside one eighth of the gathered array, i.e. inside
 // its own 4 MiB L2.  Placement only affects speed, never results.  Returns -1 for the padding workgroups.
-__device__ __forceinline__ int tile_index(int ntiles, int remap)
+__device__ __forceinline__ int tile_index(int ntiles, int remap = 1)
 {
     const int b = blockIdx.x;
     if (!remap) return b < ntiles ? b : -1;
@@ -49,7 +50,7 @@ __device__ __forceinline__ int tile_index(int ntiles, int remap)
     const int t = (b & 7) * per + (b >> 3);
     return ((b >> 3) < per && t < ntiles) ? t : -1;
 }
-static inline int tile_grid(int ntiles, int remap) { return remap ? 8 * ((ntiles + 7) / 8) : ntiles; }
+static inline int tile_grid(int ntiles, int remap = 1) { return remap ? 8 * ((ntiles + 7) / 8) : ntiles; }
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }

@@ -18,10 +18,10 @@ __global__ __launch_bounds__(kBlock) void slice_v1_kernel(const int *__restrict_
                                                           const float *__restrict__ ew,
                                                           const uint32_t *__restrict__ perm, int n, int own_begin,
                                                           int n_own, const float *__restrict__ values, float rden,
-                                                          float *__restrict__ out, int ntiles, int remap,
+                                                          float *__restrict__ out, int ntiles,
                                                           const float *__restrict__ affine, const float *__restrict__ src)
 {
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int pl = tile * kBlock + threadIdx.x;
     if (pl >= n_own) return;
@@ -53,11 +53,11 @@ __global__ __launch_bounds__(kBlock) void slice_vec_kernel(const int *__restrict
                                                            const uint32_t *__restrict__ perm, int n, int own_begin,
                                                            int n_own, int d1, const float4 *__restrict__ values,
                                                            int nch, int vd, float rden, float *__restrict__ out,
-                                                           int ntiles, int remap, const float *__restrict__ affine,
+                                                           int ntiles, const float *__restrict__ affine,
                                                            const float *__restrict__ src, float *__restrict__ dot_partial)
 {
     __shared__ float4 red[kBlock];
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;                                  // the whole workgroup leaves together
     const int64_t item = (int64_t)tile * kBlock + threadIdx.x;
     const bool live = item < (int64_t)n_own * nch;
@@ -159,10 +159,10 @@ int slice_impl(plx_lattice *L, const float *d_values, int vd, float *d_out, hipS
     const int n = (int)L->n, ob = (int)L->own_begin;
     if (vd == 1) {
         const int nt = ceil_div(n_own, kBlock);
-        const int grid = tile_grid(nt, g_xcd_remap);
+        const int grid = tile_grid(nt);
         switch (L->d + 1) {
 #define PLX_CASE(D1) \
-    case D1: slice_v1_kernel<D1><<<grid, kBlock, 0, stream>>>(evid, ew, perm, n, ob, n_own, d_values, 1.0f / L->slice_denom, d_out, nt, g_xcd_remap, d_affine, d_src); break;
+    case D1: slice_v1_kernel<D1><<<grid, kBlock, 0, stream>>>(evid, ew, perm, n, ob, n_own, d_values, 1.0f / L->slice_denom, d_out, nt, d_affine, d_src); break;
             PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9)
             PLX_CASE(10) PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17)
             PLX_CASE(18) PLX_CASE(19) PLX_CASE(20) PLX_CASE(21) PLX_CASE(22) PLX_CASE(23) PLX_CASE(24) PLX_CASE(25)
@@ -194,15 +194,15 @@ int slice_impl(plx_lattice *L, const float *d_values, int vd, float *d_out, hipS
         const int nt = ceil_div((int64_t)n_own * nch, kBlock);
         const float4 *v4 = reinterpret_cast<const float4 *>(d_values);
         const float rden = 1.0f / L->slice_denom;
-        const int grid = tile_grid(nt, g_xcd_remap);
+        const int grid = tile_grid(nt);
         switch (L->d + 1 <= kSliceMaxD1 ? L->d + 1 : 0) {
 #define PLX_CASE(D1) \
-    case D1: slice_vec_kernel<D1><<<grid, kBlock, 0, stream>>>(evid, ew, perm, n, ob, n_own, L->d + 1, v4, nch, slice_vd, rden, slice_out, nt, g_xcd_remap, slice_affine, d_src, d_dot_partial); break;
+    case D1: slice_vec_kernel<D1><<<grid, kBlock, 0, stream>>>(evid, ew, perm, n, ob, n_own, L->d + 1, v4, nch, slice_vd, rden, slice_out, nt, slice_affine, d_src, d_dot_partial); break;
             PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9) PLX_CASE(10)
             PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17) PLX_CASE(18)
             PLX_CASE(19) PLX_CASE(20)
 #undef PLX_CASE
-        default: slice_vec_kernel<0><<<grid, kBlock, 0, stream>>>(evid, ew, perm, n, ob, n_own, L->d + 1, v4, nch, slice_vd, rden, slice_out, nt, g_xcd_remap, slice_affine, d_src, d_dot_partial); break;
+        default: slice_vec_kernel<0><<<grid, kBlock, 0, stream>>>(evid, ew, perm, n, ob, n_own, L->d + 1, v4, nch, slice_vd, rden, slice_out, nt, slice_affine, d_src, d_dot_partial); break;
         }
         if (two_step) {
             L->kn_slice = "slice_vec_kernel+unpermute_rows_kernel";
@@ -229,10 +229,10 @@ __global__ __launch_bounds__(kBlock) void slice_contract_kernel(const int *__res
                                                                 int n_own, int d1, const float4 *__restrict__ values,
                                                                 int nch, const float *__restrict__ rec, int recw, int L,
                                                                 int d, float rden, float *__restrict__ grad_x,
-                                                                float *__restrict__ grad_src, int ntiles, int remap)
+                                                                float *__restrict__ grad_src, int ntiles)
 {
     __shared__ float4 f4s[kBlock / 64][64 * MAXCH];
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pl = tile * (kBlock / 64) + wave;
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(kBlock) void slice_contract_d_kernel(const int *__r
                                                                   int n_own, const float4 *__restrict__ values, int nch,
                                                                   const float *__restrict__ rec, int recw, int L, float rden,
                                                                   float *__restrict__ grad_x, float *__restrict__ grad_src,
-                                                                  int ntiles, int remap)
+                                                                  int ntiles)
 {
     constexpr int d = D1 - 1;
     constexpr int DK = d <= 1 ? 1 : d <= 2 ? 2 : d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : 32;   // lanes per l-group
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(kBlock) void slice_contract_d_kernel(const int *__r
     constexpr int RB = (kContractLoads / MAXCH) < D1 ? (kContractLoads / MAXCH) : D1;           // rows in flight
     __shared__ float4 f4s[kBlock / 64][64 * MAXCH];
     __shared__ float recs[kBlock / 64][64];
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pl0 = tile * (kBlock / 64) * PPW + wave;
@@ -419,10 +419,10 @@ static bool launch_slice_contract_d(plx_lattice *lat, const float4 *res, int nch
     const int n_own = (int)(lat->own_end - lat->own_begin);
     const uint32_t *perm = lat->lattice_rows ? nullptr : lat->perm.as<uint32_t>();
     const int nt = ceil_div(n_own, (kBlock / 64) * kContractPoints);
-    const int grid = tile_grid(nt, g_xcd_remap);
+    const int grid = tile_grid(nt);
     switch (lat->d + 1) {
 #define PLX_CASE(D1) \
-    case D1: slice_contract_d_kernel<D1, MAXCH><<<grid, kBlock, 0, stream>>>(lat->evid.as<int>(), lat->ew.as<float>(), perm, (int)lat->n, (int)lat->own_begin, n_own, res, nch, rec, recw, L, 1.0f / lat->slice_denom, d_grad_x, d_grad_src, nt, g_xcd_remap); return true;
+    case D1: slice_contract_d_kernel<D1, MAXCH><<<grid, kBlock, 0, stream>>>(lat->evid.as<int>(), lat->ew.as<float>(), perm, (int)lat->n, (int)lat->own_begin, n_own, res, nch, rec, recw, L, 1.0f / lat->slice_denom, d_grad_x, d_grad_src, nt); return true;
         PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9) PLX_CASE(10)
         PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17) PLX_CASE(18)
         PLX_CASE(19) PLX_CASE(20) PLX_CASE(21)
@@ -449,7 +449,7 @@ int backward_impl(plx_lattice *lat, const float *d_g, const float *d_src, const 
     const uint32_t *perm = lat->lattice_rows ? nullptr : lat->perm.as<uint32_t>();
     const float *rec = lat->rec.as<float>();
     const int nt = ceil_div(n_own, kBlock / 64);
-    const int sgrid = tile_grid(nt, g_xcd_remap);
+    const int sgrid = tile_grid(nt);
     const bool compiled = g_contract_v != 0 &&
                           (nch <= 64 ? launch_slice_contract_d<1>(lat, res, nch, rec, recw, L, d_grad_x, d_grad_src, stream)
                                      : launch_slice_contract_d<2>(lat, res, nch, rec, recw, L, d_grad_x, d_grad_src, stream));
@@ -457,11 +457,11 @@ int backward_impl(plx_lattice *lat, const float *d_g, const float *d_src, const 
     } else if (nch <= 64)
         slice_contract_kernel<1><<<sgrid, kBlock, 0, stream>>>(lat->evid.as<int>(), lat->ew.as<float>(), perm, (int)lat->n,
                                                               (int)lat->own_begin, n_own, d + 1, res, nch, rec, recw, L, d,
-                                                              1.0f / lat->slice_denom, d_grad_x, d_grad_src, nt, g_xcd_remap);
+                                                              1.0f / lat->slice_denom, d_grad_x, d_grad_src, nt);
     else
         slice_contract_kernel<2><<<sgrid, kBlock, 0, stream>>>(lat->evid.as<int>(), lat->ew.as<float>(), perm, (int)lat->n,
                                                               (int)lat->own_begin, n_own, d + 1, res, nch, rec, recw, L, d,
-                                                              1.0f / lat->slice_denom, d_grad_x, d_grad_src, nt, g_xcd_remap);
+                                                              1.0f / lat->slice_denom, d_grad_x, d_grad_src, nt);
     tmark(lat, stream);
     PLX_HIP_TRY(hipGetLastError());
     return PLX_OK;

@@ -256,20 +256,16 @@ int sort_fill_blocks_lds(const int *evid, const float *ew, int n, int own_begin,
     const int cb = ipt == 16 ? 12 : 13;
     // packed keys: the vertex field must leave the all-ones value to the padding (ids < m < 2^vb) and fit above the corner bits
     const int vb = vbits + (((int64_t)1 << vbits) == (int64_t)m_vertices ? 1 : 0);
-    const int mode = (g_blk_sort != 0 && vb + cb <= 32) ? g_blk_sort : 0;      // 0: (key, value) pairs, 4 bits per pass
+    const bool packed = vb + cb <= 32;
 #define PLX_BLK_SORT(E, PACKED, RBITS, T)                                                                                       \
     blk_sort_fill_kernel<E, PACKED, RBITS, T><<<(unsigned)nblocks, T, (size_t)cpb * 2, stream>>>(                               \
-        evid, ew, n, own_begin, n_own, P, d1, cpb, mode ? vb : vbits, bc_pt, bc_w, srow, sstride, rows_tmp, rows)
-    // mode: 0 = (key, value) pairs, 4 bits per pass; 4 / 5 / 6 = packed keys at that many bits per pass, 256 threads;
-    // 15 = packed keys, 5 bits, 512 threads
+        evid, ew, n, own_begin, n_own, P, d1, cpb, packed ? vb : vbits, bc_pt, bc_w, srow, sstride, rows_tmp, rows)
+    // packed keys, 5 bits per pass, 512 threads; where the packed key does not fit, (key, value) pairs, 4 bits per pass,
+    // 256 threads
     if (ipt == 16) {
-        if (mode == 0) PLX_BLK_SORT(16, false, 4, 256); else if (mode == 4) PLX_BLK_SORT(16, true, 4, 256);
-        else if (mode == 6) PLX_BLK_SORT(16, true, 6, 256); else if (mode == 5) PLX_BLK_SORT(16, true, 5, 256);
-        else PLX_BLK_SORT(16, true, 5, 512);
+        if (packed) PLX_BLK_SORT(16, true, 5, 512); else PLX_BLK_SORT(16, false, 4, 256);
     } else {
-        if (mode == 0) PLX_BLK_SORT(24, false, 4, 256); else if (mode == 4) PLX_BLK_SORT(24, true, 4, 256);
-        else if (mode == 6) PLX_BLK_SORT(24, true, 6, 256); else if (mode == 5) PLX_BLK_SORT(24, true, 5, 256);
-        else PLX_BLK_SORT(24, true, 5, 512);
+        if (packed) PLX_BLK_SORT(24, true, 5, 512); else PLX_BLK_SORT(24, false, 4, 256);
     }
 #undef PLX_BLK_SORT
     PLX_HIP_TRY(hipGetLastError());

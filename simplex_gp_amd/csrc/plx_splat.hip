@@ -77,8 +77,7 @@ __global__ __launch_bounds__(kSplatBlock) void splat_scan_kernel(const int *__re
                                                             const int *__restrict__ csr_vid,
                                                             const V *__restrict__ ssrc, int rowlen, int nnz,
                                                             V *__restrict__ values, V *__restrict__ head_partial,
-                                                            V *__restrict__ tail_partial, int ablate, int nchunks,
-                                                            int remap)
+                                                            V *__restrict__ tail_partial, int ablate, int nchunks)
 {
     ablate = PLX_DIAG_VALUE(ablate);                   // diagnostics are compiled into libplx_diag.so only
     using O = VecOps<V>;
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(kSplatBlock) void splat_scan_kernel(const int *__re
     __shared__ V wave_sum[kSplatBlock / 64][NCH];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = tile_index(nchunks, remap);
+    const int c = tile_index(nchunks);
     if (c < 0) return;
     const int tile0 = blockIdx.y * NCH;
     const int k0 = c * kSplatChunk;
@@ -319,10 +318,10 @@ __global__ __launch_bounds__(kBlock) void splat_wide_kernel(const int *__restric
                                                             const S src, int nch, int nnz,
                                                             float4 *__restrict__ values,
                                                             float4 *__restrict__ head_partial,
-                                                            float4 *__restrict__ tail_partial, int ntiles, int remap)
+                                                            float4 *__restrict__ tail_partial, int ntiles)
 {
     constexpr int U = (MAXCH == 1 ? 8 : 4) / (sizeof(typename S::Raw) > 16 ? 2 : 1);   // corners in flight
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = tile * (kBlock / 64) + wave;
@@ -415,7 +414,7 @@ __global__ __launch_bounds__(kBlock) void splat_group_kernel(const int *__restri
                                                              const V *__restrict__ ssrc, int nch, int nnz,
                                                              V *__restrict__ values,
                                                              V *__restrict__ head_partial,
-                                                             V *__restrict__ tail_partial, int ntiles, int remap,
+                                                             V *__restrict__ tail_partial, int ntiles,
                                                              int ablate)
 {
     ablate = PLX_DIAG_VALUE(ablate);                   // diagnostics are compiled into libplx_diag.so only
@@ -427,7 +426,7 @@ __global__ __launch_bounds__(kBlock) void splat_group_kernel(const int *__restri
     __shared__ int lds_pt[kBlock / 64][G * RS];
     __shared__ float lds_w[kBlock / 64][G * RS];
     __shared__ int lds_vid[kBlock / 64][G * RS];
-    const int tile = tile_index(ntiles, remap);
+    const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wchunk = tile * (kBlock / 64) + wave;
@@ -642,7 +641,7 @@ int splat_impl(plx_lattice *L, const float *d_src, int vd, float *d_values, hipS
     if (vd == 1) {
         // (one lane per run of corners -- splat_group_kernel<float, 1, 16> -- was measured 18-75 % slower here:
         // the scan kernel's 16-byte index loads and coalesced stores win on single-column rows)
-        splat_scan_kernel<float, 1><<<tile_grid(nchunks, g_xcd_remap), kSplatBlock, 0, stream>>>(pt, w, vid, ss, 1, nnz, d_values, hp, tp, PLX_DIAG_VALUE(g_splat_ablate), nchunks, g_xcd_remap);
+        splat_scan_kernel<float, 1><<<tile_grid(nchunks), kSplatBlock, 0, stream>>>(pt, w, vid, ss, 1, nnz, d_values, hp, tp, PLX_DIAG_VALUE(g_splat_ablate), nchunks);
     } else {
         const float4 *s4 = reinterpret_cast<const float4 *>(ss);
         float4 *v4 = reinterpret_cast<float4 *>(d_values), *h4 = reinterpret_cast<float4 *>(hp), *t4 = reinterpret_cast<float4 *>(tp);
@@ -655,12 +654,12 @@ int splat_impl(plx_lattice *L, const float *d_src, int vd, float *d_values, hipS
             PLX_TRY(ensure(L->tail_partial, (size_t)nwide * vdp * 4));
             h4 = reinterpret_cast<float4 *>(L->head_partial.as<float>());
             t4 = reinterpret_cast<float4 *>(L->tail_partial.as<float>());
-            const int grid = tile_grid(nt, g_xcd_remap);
+            const int grid = tile_grid(nt);
             const RowSource rows{s4, nch_total};
             if (nch_total <= 64)
-                splat_wide_kernel<1, RowSource><<<grid, kBlock, 0, stream>>>(pt, w, vid, rows, nch_total, nnz, v4, h4, t4, nt, g_xcd_remap);
+                splat_wide_kernel<1, RowSource><<<grid, kBlock, 0, stream>>>(pt, w, vid, rows, nch_total, nnz, v4, h4, t4, nt);
             else
-                splat_wide_kernel<2, RowSource><<<grid, kBlock, 0, stream>>>(pt, w, vid, rows, nch_total, nnz, v4, h4, t4, nt, g_xcd_remap);
+                splat_wide_kernel<2, RowSource><<<grid, kBlock, 0, stream>>>(pt, w, vid, rows, nch_total, nnz, v4, h4, t4, nt);
             splat_fixup_kernel<<<ceil_div((int64_t)nwide * vdp, kBlock), kBlock, 0, stream>>>(
                 pt, vid, nwide, kWideChunk, nnz, vdp, L->head_partial.as<float>(), L->tail_partial.as<float>(), d_values);
             L->kn_splat = gathered ? "gather_in_kernel+splat_wide_kernel+splat_fixup_kernel" : "splat_wide_kernel+splat_fixup_kernel";
@@ -677,13 +676,13 @@ int splat_impl(plx_lattice *L, const float *d_src, int vd, float *d_values, hipS
             PLX_TRY(ensure(L->tail_partial, (size_t)nwchunks * vdp * 4));
             h4 = reinterpret_cast<float4 *>(L->head_partial.as<float>());
             t4 = reinterpret_cast<float4 *>(L->tail_partial.as<float>());
-            const int grid = tile_grid(nt, g_xcd_remap);
+            const int grid = tile_grid(nt);
             switch (nchp) {
-            case 2: splat_group_kernel<float4, 2, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, g_xcd_remap, PLX_DIAG_VALUE(g_splat_ablate)); break;
-            case 3: splat_group_kernel<float4, 3, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, g_xcd_remap, PLX_DIAG_VALUE(g_splat_ablate)); break;
-            case 4: splat_group_kernel<float4, 4, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, g_xcd_remap, PLX_DIAG_VALUE(g_splat_ablate)); break;
-            case 8: splat_group_kernel<float4, 8, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, g_xcd_remap, PLX_DIAG_VALUE(g_splat_ablate)); break;
-            default: splat_group_kernel<float4, 16, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, g_xcd_remap, PLX_DIAG_VALUE(g_splat_ablate)); break;
+            case 2: splat_group_kernel<float4, 2, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, PLX_DIAG_VALUE(g_splat_ablate)); break;
+            case 3: splat_group_kernel<float4, 3, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, PLX_DIAG_VALUE(g_splat_ablate)); break;
+            case 4: splat_group_kernel<float4, 4, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, PLX_DIAG_VALUE(g_splat_ablate)); break;
+            case 8: splat_group_kernel<float4, 8, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, PLX_DIAG_VALUE(g_splat_ablate)); break;
+            default: splat_group_kernel<float4, 16, kGroupRun><<<grid, kBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, nt, PLX_DIAG_VALUE(g_splat_ablate)); break;
             }
             splat_fixup_kernel<<<ceil_div((int64_t)nwchunks * vdp, kBlock), kBlock, 0, stream>>>(
                 pt, vid, nwchunks, wc, nnz, vdp, L->head_partial.as<float>(), L->tail_partial.as<float>(), d_values);
@@ -694,11 +693,11 @@ int splat_impl(plx_lattice *L, const float *d_src, int vd, float *d_values, hipS
         }
         // up to 3 chunks (12 columns) per workgroup in registers; wider rows take more column tiles
         const int nch = nch_total <= 3 ? nch_total : (nch_total % 3 == 0 ? 3 : (nch_total % 2 == 0 ? 2 : 3));
-        dim3 grid((unsigned)tile_grid(nchunks, g_xcd_remap), (unsigned)ceil_div(nch_total, nch));
+        dim3 grid((unsigned)tile_grid(nchunks), (unsigned)ceil_div(nch_total, nch));
         switch (nch) {
-        case 1: splat_scan_kernel<float4, 1><<<grid, kSplatBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, PLX_DIAG_VALUE(g_splat_ablate), nchunks, g_xcd_remap); break;
-        case 2: splat_scan_kernel<float4, 2><<<grid, kSplatBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, PLX_DIAG_VALUE(g_splat_ablate), nchunks, g_xcd_remap); break;
-        default: splat_scan_kernel<float4, 3><<<grid, kSplatBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, PLX_DIAG_VALUE(g_splat_ablate), nchunks, g_xcd_remap); break;
+        case 1: splat_scan_kernel<float4, 1><<<grid, kSplatBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, PLX_DIAG_VALUE(g_splat_ablate), nchunks); break;
+        case 2: splat_scan_kernel<float4, 2><<<grid, kSplatBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, PLX_DIAG_VALUE(g_splat_ablate), nchunks); break;
+        default: splat_scan_kernel<float4, 3><<<grid, kSplatBlock, 0, stream>>>(pt, w, vid, s4, nch_total, nnz, v4, h4, t4, PLX_DIAG_VALUE(g_splat_ablate), nchunks); break;
         }
     }
     splat_fixup_kernel<<<ceil_div((int64_t)nchunks * vdp, kBlock), kBlock, 0, stream>>>(pt, vid, nchunks, kSplatChunk, nnz, vdp,
@@ -751,11 +750,11 @@ int splat_stack_impl(plx_lattice *lat, const float *d_g, const float *d_src, con
     const int *pt = lat->csr_pt.as<int>(), *vid = lat->csr_vid.as<int>();
     const StackSource stack{rec, recw, L, d};
     const size_t wide_lds = (size_t)(kBlock / 64) * 64 * recw * 4;   // <= 64 KB: plx_apply_backward bounds recw
-    const int grid = tile_grid(nwt, g_xcd_remap);
+    const int grid = tile_grid(nwt);
     if (nch <= 64)
-        splat_wide_kernel<1, StackSource><<<grid, kBlock, wide_lds, stream>>>(pt, lat->csr_w.as<float>(), vid, stack, nch, nnz, v4, h4, t4, nwt, g_xcd_remap);
+        splat_wide_kernel<1, StackSource><<<grid, kBlock, wide_lds, stream>>>(pt, lat->csr_w.as<float>(), vid, stack, nch, nnz, v4, h4, t4, nwt);
     else
-        splat_wide_kernel<2, StackSource><<<grid, kBlock, wide_lds, stream>>>(pt, lat->csr_w.as<float>(), vid, stack, nch, nnz, v4, h4, t4, nwt, g_xcd_remap);
+        splat_wide_kernel<2, StackSource><<<grid, kBlock, wide_lds, stream>>>(pt, lat->csr_w.as<float>(), vid, stack, nch, nnz, v4, h4, t4, nwt);
     splat_fixup_kernel<<<ceil_div((int64_t)nwide * vdp, kBlock), kBlock, 0, stream>>>(
         pt, vid, nwide, kWideChunk, nnz, vdp, lat->head_partial.as<float>(), lat->tail_partial.as<float>(), d_values);
     lat->kn_splat = "backward_pack_kernel+splat_wide_kernel+splat_fixup_kernel";

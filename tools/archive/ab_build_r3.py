@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Wall time of plx_build + plx_prepare(vd) (ms, best of several, synchronised at both ends) for plx_tune variants.
-    python tools/ab_build_r3.py --n 1000000 --ell 1.0 --variants "order_compact=0" "order_compact=1" """
+    python tools/ab_build_r3.py --n 1000000 --ell 1.0 --variants "insert_dedupe=1" "insert_dedupe=2" """
 import argparse, os, sys, time, json
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,7 +16,7 @@ ap.add_argument("--variants", nargs="*", default=[""])
 args = ap.parse_args()
 x, v = bench.synth(args.n, args.d, args.vd)
 ref = (x / args.ell).contiguous().cuda()
-DEFAULTS = {"order_compact": 1, "block_e": 0, "vertex_order": 1, "sort_points": 1, "order_zcurve": 1, "insert_dedupe": 2}
+DEFAULTS = {"block_e": 0, "vertex_order": 1, "sort_points": 1, "insert_dedupe": 2}
 lat = plx.Lattice()
 for var in args.variants:
     for k, val in DEFAULTS.items():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The bench's timed loop (one build + K MVMs, no synchronisation inside) for plx_tune variants: us per step.
-    python tools/ab_loop_r3.py --steps 20 --variants "order_compact=0" "order_compact=1" "readback_spin=0" """
+    python tools/ab_loop_r3.py --steps 20 --variants "block_e=16" "block_e=24" """
 import argparse, os, sys, time, json
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,7 +15,7 @@ ap.add_argument("--variants", nargs="*", default=[""])
 args = ap.parse_args()
 x, v = bench.synth(args.n, 8, 1)
 ref = (x / args.ell).contiguous().cuda(); v = v.cuda(); out = torch.empty_like(v)
-DEFAULTS = {"order_compact": 1, "readback_spin": 1, "block_e": 0}
+DEFAULTS = {"block_e": 0}
 lat = plx.Lattice()
 for var in args.variants:
     for k, val in DEFAULTS.items():

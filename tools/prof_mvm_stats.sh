@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX: per-kernel table (rocprofv3 --stats) of tools/prof_mvm.py for each plx_tune setting in TUNES.
-#   TUNES="order_zcurve=1 order_zcurve=2" ELL=1.0 EXTRA="--vd 1" tools/prof_mvm_stats.sh
+#   TUNES="vertex_order=1 vertex_order=2" ELL=1.0 EXTRA="--vd 1" tools/prof_mvm_stats.sh
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 for T in ${TUNES:-vertex_order=1}; do
