@@ -260,6 +260,41 @@ int plx_apply_rows(plx_lattice *lat, const float *d_src, int64_t src_begin, int6
 int plx_last_rows_kernels(const plx_lattice *lat, char *buf, int cap);
 
 /*
+ * The float64 product (callers detect it by symbol; the version string is unchanged).  The operator is the one plx_apply
+ * applies, carried in double: the vertex ids, the neighbour table, the fp32 barycentric weights and the fp32 taps of the
+ * build, each converted exactly to double, every sum in double, the result divided by 1 + 2^-d in double.  The lattice
+ * itself is the fp32 build's -- positions that a caller holds in double are rounded to float for plx_build, so one build
+ * serves both precisions.  What double buys is an accurately APPLIED operator (solves that converge below the 1e-7 at
+ * which fp32 products stall), not a more accurate embedding: the lattice approximates the exact kernel to 0.07-0.57
+ * relative error either way.  The operator is neither symmetric nor positive (the d + 1 blur passes do not commute), in
+ * either precision.
+ *   plx_values_stride_f64  doubles per vertex row: 1 for vd = 1, otherwise vd rounded up to a multiple of 2 (rows are
+ *                          whole 16-byte vectors); -1 for vd < 1.  d_values / d_scratch below are [m][stride].
+ *   plx_splat_f64 / plx_blur_f64 / plx_slice_f64  the three stages on caller buffers of doubles, as plx_splat / plx_blur /
+ *                          plx_slice; d_values and d_scratch are distinct and, for vd > 1, 16-byte aligned.
+ *   plx_apply_f64          splat -> blur -> slice on a float64 workspace of the lattice: two value planes of doubles,
+ *                          allocated by the first fp64 call of a width (fp32 use never allocates them).
+ *   plx_last_f64_kernels   "splat=...;blur_axis=...;slice=..." of the last fp64 call (plx_last_kernels goes on naming the
+ *                          fp32 stages only).
+ * Rows of d_src [n][vd] and d_out [n][vd] are ALWAYS in the caller's order, whatever plx_set_row_order says; they need
+ * 8-byte alignment only.  Scope and refusals are those of plx_apply_rows: plain single-shard builds (plx_build or
+ * plx_filter); a sharded or merged lattice and a build that replayed "reference_growth" return PLX_ERR_STATE.  Every
+ * argument is checked before any GPU work: NULL pointers, vd < 1, misaligned buffers are PLX_ERR_INVALID; m * stride and
+ * n * stride stay under 2^31 elements (PLX_ERR_TOO_LARGE).
+ * Deterministic: the splat gathers by vertex over the vertex-sorted corners in order, no float atomics; two calls with the
+ * same arguments are bit-equal, and the staged calls give the bits of plx_apply_f64.
+ * The first fp64 splat after a build makes the vertex-sorted corner table and its row pointer (no read-back), and the
+ * first plx_apply_f64 of a width grows the workspace; under stream capture such a call returns PLX_ERR_STATE.  Later
+ * calls neither allocate nor synchronise (plx_device_bytes does not move) and are graph-capturable.
+ */
+int plx_values_stride_f64(int vd);
+int plx_splat_f64(plx_lattice *lat, const double *d_src, int vd, double *d_values, void *stream);
+int plx_blur_f64(plx_lattice *lat, double *d_values, double *d_scratch, int vd, int *result_in_scratch, void *stream);
+int plx_slice_f64(plx_lattice *lat, const double *d_values, int vd, double *d_out, void *stream);
+int plx_apply_f64(plx_lattice *lat, const double *d_src, int vd, double *d_out, void *stream);
+int plx_last_f64_kernels(const plx_lattice *lat, char *buf, int cap);
+
+/*
  * The reference's one-shot call (cpp:6-10 -> h:259-340): build a lattice for
  * d_ref, apply it to d_src, leave nothing behind.  `scratch` may be NULL or a
  * lattice object whose buffers are reused (avoids hipMalloc in steady state; it

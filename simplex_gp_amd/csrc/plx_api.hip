@@ -83,7 +83,7 @@ static std::vector<DevBuf *> all_bufs(plx_lattice *L)
             &L->head_partial, &L->tail_partial, &L->val_a, &L->val_b, &L->ssrc, &L->rec, &L->perm, &L->iota, &L->cmask, &L->cbase, &L->cids, &L->merge_slot, &L->merge_flags,
             &L->sortkey_in, &L->sortkey_out,
             &L->bc_pt, &L->bc_w, &L->srow, &L->brow_ptr, &L->brow_vid, &L->s2_idx, &L->s2_ptr, &L->s2_vid, &L->s2_wave, &L->s2_wave_v, &L->partial, &L->pair_nbr, &L->inv_perm, &L->vslot, &L->vkeys_alt, &L->vslot_alt, &L->vorder,
-            &L->rows_cnt, &L->rows_vid};
+            &L->rows_cnt, &L->rows_vid, &L->val64_a, &L->val64_b};
     for (auto &r : L->rows)
         for (DevBuf *b : {&r.ptr, &r.row, &r.w, &r.pos, &r.prow}) v.push_back(b);
     return v;
@@ -534,6 +534,84 @@ int plx_last_rows_kernels(const plx_lattice *L, char *buf, int cap)
 {
     if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
     snprintf(buf, (size_t)cap, "splat=%s;slice=%s", L->kn_rows_splat, L->kn_rows_slice);
+    return PLX_OK;
+}
+
+// ---- the float64 product (kernels: plx_f64.hip) ------------------------------------------------------------------------
+
+int plx_values_stride_f64(int vd) { return vd >= 1 ? values_stride_f64(vd) : -1; }
+
+// Everything an fp64 call checks before any GPU work.  `a` / `b`: the call's two buffers of doubles.
+static int check_f64(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
+{
+    if (!L || !a || !b) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
+    if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    if ((((uintptr_t)a | (uintptr_t)b) & 7) != 0) { set_error("%s: buffers of doubles must be 8-byte aligned", who); return PLX_ERR_INVALID; }
+    if (L->n_shards != 1 || L->partial_cover) {
+        set_error("%s: sharded or merged lattice (the float64 product is served by plain single-shard builds only)", who);
+        return PLX_ERR_STATE;
+    }
+    if (L->replay.active) {
+        set_error("%s: this build replayed \"reference_growth\" (its splat and slice sides differ); the float64 product is "
+                  "not served on it", who);
+        return PLX_ERR_STATE;
+    }
+    if ((int64_t)L->m * values_stride_f64(vd) >= (1ll << 31) || (int64_t)L->n * values_stride_f64(vd) >= (1ll << 31)) {
+        set_error("%s: m*vd or n*vd exceeds 2^31 elements; split the columns", who);
+        return PLX_ERR_TOO_LARGE;
+    }
+    return PLX_OK;
+}
+
+int plx_splat_f64(plx_lattice *L, const double *d_src, int vd, double *d_values, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_src, d_values, vd, "plx_splat_f64"));
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_splat_f64"));
+    DeviceGuard g(L->device);
+    return splat_f64_impl(L, d_src, vd, d_values, (hipStream_t)stream);
+}
+
+int plx_blur_f64(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_values, d_scratch, vd, "plx_blur_f64"));
+    if (!result_in_scratch) { set_error("plx_blur_f64: result_in_scratch is NULL"); return PLX_ERR_INVALID; }
+    if (d_values == d_scratch) { set_error("plx_blur_f64: d_values and d_scratch must be different buffers"); return PLX_ERR_INVALID; }
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_f64"));
+    PLX_TRY(check_values_aligned(d_scratch, vd, "plx_blur_f64"));
+    DeviceGuard g(L->device);
+    return blur_f64_impl(L, d_values, d_scratch, vd, result_in_scratch, (hipStream_t)stream);
+}
+
+int plx_slice_f64(plx_lattice *L, const double *d_values, int vd, double *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_values, d_out, vd, "plx_slice_f64"));
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_slice_f64"));
+    DeviceGuard g(L->device);
+    return slice_f64_impl(L, d_values, vd, d_out, (hipStream_t)stream);
+}
+
+int plx_apply_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_src, d_out, vd, "plx_apply_f64"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    PLX_TRY(ensure(L->val64_a, (size_t)L->m * values_stride_f64(vd) * 8));
+    PLX_TRY(ensure(L->val64_b, (size_t)L->m * values_stride_f64(vd) * 8));
+    PLX_TRY(splat_f64_impl(L, d_src, vd, L->val64_a.as<double>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), vd, &in_b, s));
+    return slice_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, d_out, s);
+}
+
+int plx_last_f64_kernels(const plx_lattice *L, char *buf, int cap)
+{
+    if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
+    snprintf(buf, (size_t)cap, "splat=%s;blur_axis=%s;slice=%s", L->kn_f64_splat, L->kn_f64_blur, L->kn_f64_slice);
     return PLX_OK;
 }
 

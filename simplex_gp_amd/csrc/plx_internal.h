@@ -287,6 +287,12 @@ struct plx_lattice {
     plx::DevBuf rows_cnt, rows_vid;           // int32 scratch of the table builds: per-tile counts, vertex of every kept corner
     const char *kn_rows_splat = "", *kn_rows_slice = "";   // kernels of the last rows call (plx_last_rows_kernels)
 
+    // the float64 product (plx_f64.hip): two value planes of doubles, allocated by the first plx_apply_f64 (never by fp32
+    // use), and the build whose vertex row pointer (row_ptr, over ensure_csr's corners) the fp64 splat has at hand
+    plx::DevBuf val64_a, val64_b;             // double [m][plx_values_stride_f64(vd)]
+    uint64_t f64_gen = 0;                     // build_gen of that build (0: none)
+    const char *kn_f64_splat = "", *kn_f64_blur = "", *kn_f64_slice = "";   // kernels of the last fp64 call (plx_last_f64_kernels)
+
     int32_t *h_pinned = nullptr;   // pinned host staging (exports)
     int *h_mail = nullptr;         // mailbox of read_back: coherent pinned host memory, word 0 = sequence number, then up to 62 values
     int mail_seq = 0;
@@ -364,6 +370,10 @@ int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t c
                     hipStream_t stream);
 int slice_rows_impl(plx_lattice *L, const float *d_values, int vd, int64_t begin, int64_t count, float *d_out,
                     hipStream_t stream);
+// plx_f64.hip: the three stages in float64 on caller buffers of doubles (arguments checked by the entry points)
+int splat_f64_impl(plx_lattice *L, const double *d_src, int vd, double *d_values, hipStream_t stream);
+int blur_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
+int slice_f64_impl(plx_lattice *L, const double *d_values, int vd, double *d_out, hipStream_t stream);
 // plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
 int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,
@@ -387,6 +397,8 @@ const Tunable *tunables();
 // value-row stride in floats: 1 for a single column, else the column count rounded up to 4 so
 // that every row is a whole number of 16-byte vectors
 inline int values_stride(int vd) { return vd == 1 ? 1 : (vd + 3) & ~3; }
+// ... and in doubles (the float64 product): 1, else the column count rounded up to 2
+inline int values_stride_f64(int vd) { return vd == 1 ? 1 : (vd + 1) & ~1; }
 
 // contiguous near-equal row blocks: the first n % shards blocks get one extra row
 inline void shard_range(int64_t n, int shards, int index, int64_t *lo, int64_t *hi)

@@ -34,10 +34,17 @@ std::vector<float> taps_of(const at::Tensor &coeffs)
     return std::vector<float>(t.data_ptr<float>(), t.data_ptr<float>() + t.numel());
 }
 
+// float64 is served where BOTH tensors are float64 (plx_apply_f64: the fp32 lattice of the rounded positions, every sum
+// in double); everything else, a mixed pair included, must be float32
+bool is_f64_pair(const at::Tensor &src, const at::Tensor &ref)
+{
+    return src.scalar_type() == at::kDouble && ref.scalar_type() == at::kDouble;
+}
+
 void check_pair(const at::Tensor &src, const at::Tensor &ref)
 {
     PLX_CHECK_CUDA(src); PLX_CHECK_CUDA(ref);
-    PLX_CHECK_F32(src); PLX_CHECK_F32(ref);
+    if (!is_f64_pair(src, ref)) { PLX_CHECK_F32(src); PLX_CHECK_F32(ref); }
     PLX_CHECK_2D(src); PLX_CHECK_2D(ref);
     TORCH_CHECK(src.size(0) == ref.size(0), "Incompatible shapes ", src.sizes(), ", and ", ref.sizes());   // py:84-85
     TORCH_CHECK(src.get_device() == ref.get_device(), "src and ref must be on the same device");
@@ -57,9 +64,10 @@ struct LatticeHandle {
 
     void build(const at::Tensor &ref_in, const at::Tensor &coeffs)
     {
-        PLX_CHECK_CUDA(ref_in); PLX_CHECK_F32(ref_in); PLX_CHECK_2D(ref_in);
+        PLX_CHECK_CUDA(ref_in); PLX_CHECK_2D(ref_in);
+        if (ref_in.scalar_type() != at::kDouble) PLX_CHECK_F32(ref_in);
         TORCH_CHECK(ref_in.get_device() == device, "lattice lives on device ", device);
-        ref = ref_in.contiguous();
+        ref = ref_in.to(at::kFloat).contiguous();           // float64 positions are rounded: the lattice is the fp32 build's
         const std::vector<float> taps = taps_of(coeffs);
         const c10::hip::HIPGuard guard(device);
         void *stream = (void *)c10::hip::getCurrentHIPStream(device).stream();
@@ -73,7 +81,9 @@ struct LatticeHandle {
 
     at::Tensor apply(const at::Tensor &src_in)
     {
-        PLX_CHECK_CUDA(src_in); PLX_CHECK_F32(src_in); PLX_CHECK_2D(src_in);
+        PLX_CHECK_CUDA(src_in); PLX_CHECK_2D(src_in);
+        const bool f64 = src_in.scalar_type() == at::kDouble;
+        if (!f64) PLX_CHECK_F32(src_in);
         TORCH_CHECK(src_in.size(0) == plx_num_points(lat), "Incompatible shapes: ", src_in.sizes(), " for a lattice of ",
                     plx_num_points(lat), " points");
         const at::Tensor src = src_in.contiguous();
@@ -83,9 +93,10 @@ struct LatticeHandle {
         int rc;
         {
             pybind11::gil_scoped_release nogil;
-            rc = plx_apply(lat, src.data_ptr<float>(), (int)src.size(1), out.data_ptr<float>(), stream);
+            rc = f64 ? plx_apply_f64(lat, src.data_ptr<double>(), (int)src.size(1), out.data_ptr<double>(), stream)
+                     : plx_apply(lat, src.data_ptr<float>(), (int)src.size(1), out.data_ptr<float>(), stream);
         }
-        TORCH_CHECK(rc == PLX_OK, "plx_apply: ", plx_last_error());
+        TORCH_CHECK(rc == PLX_OK, f64 ? "plx_apply_f64: " : "plx_apply: ", plx_last_error());
         return out;
     }
 
@@ -100,8 +111,9 @@ std::unordered_map<int, std::unique_ptr<LatticeHandle>> g_scratch;
 at::Tensor filter(at::Tensor src, at::Tensor ref, at::Tensor coeffs)
 {
     check_pair(src, ref);
+    const bool f64 = is_f64_pair(src, ref);
     src = src.contiguous();                                 // the reference passes reference.contiguous() only (py:95)
-    ref = ref.contiguous();
+    ref = ref.to(at::kFloat).contiguous();                  // float64 positions are rounded for the build
     const std::vector<float> taps = taps_of(coeffs);
     const int dev = (int)src.get_device();
     at::Tensor out = at::empty_like(src);
@@ -114,10 +126,18 @@ at::Tensor filter(at::Tensor src, at::Tensor ref, at::Tensor coeffs)
         std::lock_guard<std::mutex> lock(g_mutex);         // one scratch lattice per device: not for concurrent use
         auto &slot = g_scratch[dev];
         if (!slot) slot.reset(new LatticeHandle(dev));
-        rc = plx_filter(slot->lat, src.data_ptr<float>(), ref.data_ptr<float>(), src.size(0), (int)ref.size(1), (int)src.size(1),
-                        taps.data(), (int)taps.size(), out.data_ptr<float>(), stream);
+        if (f64) {
+            // the fp64 product runs on a lattice built as usual; there is no one-shot form of it
+            rc = plx_build(slot->lat, ref.data_ptr<float>(), src.size(0), (int)ref.size(1), taps.data(), (int)taps.size(), 0, 1,
+                           stream);
+            if (rc == PLX_OK)
+                rc = plx_apply_f64(slot->lat, src.data_ptr<double>(), (int)src.size(1), out.data_ptr<double>(), stream);
+        } else {
+            rc = plx_filter(slot->lat, src.data_ptr<float>(), ref.data_ptr<float>(), src.size(0), (int)ref.size(1),
+                            (int)src.size(1), taps.data(), (int)taps.size(), out.data_ptr<float>(), stream);
+        }
     }
-    TORCH_CHECK(rc == PLX_OK, "plx_filter: ", plx_last_error());
+    TORCH_CHECK(rc == PLX_OK, f64 ? "plx_build + plx_apply_f64: " : "plx_filter: ", plx_last_error());
     return out;
 }
 

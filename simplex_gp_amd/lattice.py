@@ -28,15 +28,24 @@ def _taps_array(coeffs):
     return taps
 
 
-def _check_f32_cuda(t, name, ndim=2):
+def _check_f32_cuda(t, name, ndim=2, f64_ok=False):
+    """f64_ok: the call has a float64 form (the stages and the product, not the build or the rows calls)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not t.is_cuda:
         raise ValueError(f"{name} must be a CUDA (HIP) tensor; this build has no CPU path")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if t.dtype != torch.float32 and not (f64_ok and t.dtype == torch.float64):
+        raise TypeError(f"{name} must be float32{' or float64' if f64_ok else ''}, got {t.dtype}")
     if t.dim() != ndim:
         raise ValueError(f"{name} must be {ndim}-D, got shape {tuple(t.shape)}")
+
+
+def _positions_f32(ref, name="ref"):
+    """The positions a lattice is built on: float32.  float64 positions are ROUNDED to float32 -- the float64 product runs
+    on the fp32 build's lattice (its error against the exact kernel is the lattice's, not the embedding's), so one build
+    serves both precisions."""
+    _check_f32_cuda(ref, name, f64_ok=True)
+    return ref if ref.dtype == torch.float32 else ref.to(torch.float32)
 
 
 class Lattice:
@@ -271,30 +280,39 @@ class Lattice:
         return {"splat": t[0], "blur": t[1], "slice": t[2]}
 
     # -- stages -----------------------------------------------------------
-    def _src(self, src, rows):
-        _check_f32_cuda(src, "src")
+    def _src(self, src, rows, f64_ok=False):
+        _check_f32_cuda(src, "src", f64_ok=f64_ok)
         if src.shape[0] != rows:
             raise ValueError(f"Incompatible shapes {tuple(src.shape)}, expected {rows} rows")
         return src.contiguous()
 
+    # The stages and the product dispatch on the dtype of the values: float32 runs the kernels the build was made for,
+    # float64 (plx_*_f64) the same structure with the fp32 weights and taps converted exactly and every sum in double.
+    # float64 rows are always in the caller's order, on plain single-shard builds only (PlxError otherwise).
     @staticmethod
-    def values_stride(vd):
-        """Floats per vertex row of a values buffer (vd rounded up to 4 when vd > 1)."""
+    def values_stride(vd, dtype=torch.float32):
+        """Elements per vertex row of a values buffer: vd rounded up to 4 floats, or to 2 doubles, when vd > 1."""
+        if dtype == torch.float64:
+            return int(nv.lib().plx_values_stride_f64(vd))
         return int(nv.lib().plx_values_stride(vd))
 
-    def new_values(self, vd):
-        """Vertex accumulator [m, values_stride(vd)]; columns >= vd are zero padding."""
-        return torch.empty((self.m, self.values_stride(vd)), dtype=torch.float32, device=self.device)
+    def new_values(self, vd, dtype=torch.float32):
+        """Vertex accumulator [m, values_stride(vd, dtype)]; columns >= vd are zero padding."""
+        return torch.empty((self.m, self.values_stride(vd, dtype)), dtype=dtype, device=self.device)
 
     def splat(self, src, values=None):
-        src = self._src(src, self.n_owned)
+        src = self._src(src, self.n_owned, f64_ok=True)
         vd = src.shape[1]
+        f64 = src.dtype == torch.float64
         if values is None:
-            values = self.new_values(vd)
+            values = self.new_values(vd, src.dtype)
+        elif values.dtype != src.dtype:
+            raise TypeError(f"values must be {src.dtype} like src, got {values.dtype}")
+        fn, name = (nv.lib().plx_splat_f64, "plx_splat_f64") if f64 else (nv.lib().plx_splat, "plx_splat")
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_splat(self._h, ctypes.c_void_p(src.data_ptr()), vd,
-                                    ctypes.c_void_p(values.data_ptr()), _stream_ptr(self.device))
-        nv.check(rc, "plx_splat")
+            rc = fn(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(values.data_ptr()),
+                    _stream_ptr(self.device))
+        nv.check(rc, name)
         return values
 
     def splat_onehot(self, points, nb, values, vd=None):
@@ -330,45 +348,66 @@ class Lattice:
     def blur(self, values, scratch=None, vd=None):
         """Returns the tensor holding the blurred values (either `values` or `scratch`).
         `values` is [m, values_stride(vd)]; vd defaults to its width."""
-        _check_f32_cuda(values, "values")
+        _check_f32_cuda(values, "values", f64_ok=True)
         vd = values.shape[1] if vd is None else vd
-        assert values.shape[1] == self.values_stride(vd) and values.is_contiguous()
+        assert values.shape[1] == self.values_stride(vd, values.dtype) and values.is_contiguous()
         if values.shape[0] < self.m:
             raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
         if scratch is None:
             scratch = torch.empty_like(values)
-        elif scratch.numel() < values.numel() or not scratch.is_contiguous():
-            raise ValueError("scratch must be a contiguous buffer at least as large as values")
+        elif scratch.numel() < values.numel() or not scratch.is_contiguous() or scratch.dtype != values.dtype:
+            raise ValueError("scratch must be a contiguous buffer of the values' dtype, at least as large as values")
         flag = ctypes.c_int(0)
+        f64 = values.dtype == torch.float64
+        fn, name = (nv.lib().plx_blur_f64, "plx_blur_f64") if f64 else (nv.lib().plx_blur, "plx_blur")
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_blur(self._h, ctypes.c_void_p(values.data_ptr()),
-                                   ctypes.c_void_p(scratch.data_ptr()), vd, ctypes.byref(flag),
-                                   _stream_ptr(self.device))
-        nv.check(rc, "plx_blur")
+            rc = fn(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), vd,
+                    ctypes.byref(flag), _stream_ptr(self.device))
+        nv.check(rc, name)
         return scratch if flag.value else values
 
     def slice(self, values, out=None, vd=None):
-        _check_f32_cuda(values, "values")
+        _check_f32_cuda(values, "values", f64_ok=True)
         vd = values.shape[1] if vd is None else vd
-        assert values.shape[1] == self.values_stride(vd) and values.is_contiguous()
+        assert values.shape[1] == self.values_stride(vd, values.dtype) and values.is_contiguous()
         if out is None:
-            out = torch.empty((self.n_owned, vd), dtype=torch.float32, device=self.device)
+            out = torch.empty((self.n_owned, vd), dtype=values.dtype, device=self.device)
+        elif out.dtype != values.dtype:
+            raise TypeError(f"out must be {values.dtype} like values, got {out.dtype}")
+        f64 = values.dtype == torch.float64
+        fn, name = (nv.lib().plx_slice_f64, "plx_slice_f64") if f64 else (nv.lib().plx_slice, "plx_slice")
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_slice(self._h, ctypes.c_void_p(values.data_ptr()), vd,
-                                    ctypes.c_void_p(out.data_ptr()), _stream_ptr(self.device))
-        nv.check(rc, "plx_slice")
+            rc = fn(self._h, ctypes.c_void_p(values.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                    _stream_ptr(self.device))
+        nv.check(rc, name)
         return out
 
     def apply(self, src, out=None):
-        """One MVM: out = slice(blur(splat(src))) on the lattice's own workspace."""
-        src = self._src(src, self.n_owned)
+        """One MVM: out = slice(blur(splat(src))) on the lattice's own workspace, in the dtype of `src` (float64: on a
+        workspace of doubles that the first such call allocates)."""
+        src = self._src(src, self.n_owned, f64_ok=True)
         vd = src.shape[1]
         if out is None:
-            out = torch.empty((self.n_owned, vd), dtype=torch.float32, device=self.device)
+            out = torch.empty((self.n_owned, vd), dtype=src.dtype, device=self.device)
+        elif out.dtype != src.dtype:
+            raise TypeError(f"out must be {src.dtype} like src, got {out.dtype}")
+        f64 = src.dtype == torch.float64
+        fn, name = (nv.lib().plx_apply_f64, "plx_apply_f64") if f64 else (nv.lib().plx_apply, "plx_apply")
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_apply(self._h, ctypes.c_void_p(src.data_ptr()), vd,
-                                    ctypes.c_void_p(out.data_ptr()), _stream_ptr(self.device))
-        nv.check(rc, "plx_apply")
+            rc = fn(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                    _stream_ptr(self.device))
+        nv.check(rc, name)
+        return out
+
+    def f64_kernels(self):
+        """Kernels launched by the last float64 splat / blur / slice (or apply) on this lattice: {"splat": [...],
+        "blur_axis": [...], "slice": [...]}; stage_kernels() goes on naming the fp32 stages."""
+        buf = ctypes.create_string_buffer(256)
+        nv.check(nv.lib().plx_last_f64_kernels(self._h, buf, 256), "plx_last_f64_kernels")
+        out = {}
+        for part in buf.value.decode().split(";"):
+            k, _, names = part.partition("=")
+            out[k] = [x for x in names.split("+") if x]
         return out
 
     # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
@@ -550,11 +589,20 @@ def filter(src, ref, coeffs):
 
     Builds a fresh lattice for `ref` on every call, exactly like the reference
     (permutohedral.h:272); only the device buffers are recycled between calls.
+
+    src and ref BOTH float64 (the reference's GPU path dispatches double too): the lattice is built on the positions
+    rounded to float32 and the product runs in double on it (Lattice.apply).  A mixed pair is a TypeError.
     """
-    _check_f32_cuda(src, "src")
-    _check_f32_cuda(ref, "ref")
+    both = isinstance(src, torch.Tensor) and isinstance(ref, torch.Tensor)
+    if both and src.dtype != ref.dtype:
+        raise TypeError(f"src and ref must both be float32 or both float64, got {src.dtype} and {ref.dtype}")
+    both_f64 = both and src.dtype == torch.float64
+    _check_f32_cuda(src, "src", f64_ok=both_f64)
+    _check_f32_cuda(ref, "ref", f64_ok=both_f64)
     if src.shape[0] != ref.shape[0]:
         raise ValueError("Incompatible shapes {}, and {}".format(tuple(src.shape), tuple(ref.shape)))
     if src.device != ref.device:
         raise ValueError("src and ref must be on the same device")
+    if both_f64:
+        return _scratch_lattice(src.device).build(_positions_f32(ref), coeffs).apply(src)
     return _scratch_lattice(src.device).filter_once(src, ref, coeffs)

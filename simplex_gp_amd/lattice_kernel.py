@@ -115,6 +115,12 @@ def _snapshot_scale(hint):
     return None if p is None else p.detach().clone()
 
 
+def _build_positions(ref):
+    """What Lattice.build gets for the cached position tensor `ref`: float64 positions rounded to float32 (the float64
+    product runs on the fp32 build's lattice), everything else as it is (build() does the checking)."""
+    return ref.to(torch.float32) if ref.dtype == torch.float64 else ref
+
+
 class _LatticeCache:
     """Small LRU of built lattices keyed on the position tensor and the taps.
 
@@ -124,6 +130,10 @@ class _LatticeCache:
     for every write torch knows about.  Writes that bypass the version counter
     (`x.data.copy_()`, a custom kernel or a DLPack alias writing into the same
     storage) are NOT seen: call lattice_cache().clear() after such a write.
+
+    float64 positions are keyed (and kept alive) as the tensor they are and built on their rounding to float32
+    (_build_positions): the lattice of a float64 tensor serves float64 and float32 right-hand sides alike; the same
+    positions held once in each dtype are two tensors, hence two entries.
     """
 
     def __init__(self, capacity=4):
@@ -163,7 +173,7 @@ class _LatticeCache:
                         self.same_positions += 1
                         return lat2
                     keep = 0 <= lat2.order_age < MAX_ORDER_AGE      # (an order that old is computed afresh, in place all the same)
-                    lat2.build(ref, taps, reuse_order=keep)
+                    lat2.build(_build_positions(ref), taps, reuse_order=keep)
                     self._entries[key] = (lat2, ref, _snapshot_scale(hint))
                     self.warm_rebuilds += 1 if keep else 0
                     return lat2
@@ -172,7 +182,7 @@ class _LatticeCache:
             lat = old                      # recycle the device buffers of the evicted lattice
         else:
             lat = Lattice(ref.device)
-        lat.build(ref, taps)
+        lat.build(_build_positions(ref), taps)
         self._entries[key] = (lat, ref, _snapshot_scale(hint))
         return lat
 
@@ -191,11 +201,14 @@ def lattice_cache():
 
 def cached_filter(src, ref, coeffs):
     """filter(src, ref, coeffs) with the lattice for (ref, coeffs) reused when
-    the same position tensor comes back (the CG loop, the backward pass)."""
+    the same position tensor comes back (the CG loop, the backward pass).  Both float64: the product runs in double on
+    the lattice of the positions rounded to float32 (Lattice.apply)."""
+    if isinstance(src, torch.Tensor) and isinstance(ref, torch.Tensor) and src.dtype != ref.dtype:
+        raise TypeError(f"src and ref must both be float32 or both float64 (got src {src.dtype}, ref {ref.dtype})")
     if not (isinstance(src, torch.Tensor) and src.is_cuda):
         raise ValueError("simplex_gp_amd has no CPU path: tensors must live on an MI355X (cuda) device")
-    if src.dtype != torch.float32 or ref.dtype != torch.float32:
-        raise TypeError(f"float32 only (got src {src.dtype}, ref {ref.dtype}); the reference CPU path is fp32 (h:277-278)")
+    if src.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"float32 or float64 only (got src {src.dtype}, ref {ref.dtype})")
     if not ref.is_cuda or ref.device != src.device:
         # checked before the cache is touched: a bad call must not evict a good lattice
         raise ValueError(f"src ({src.device}) and ref ({ref.device}) must live on the same MI355X (cuda) device")
@@ -242,7 +255,9 @@ class LatticeFilterGeneral(Function):
             if ctx.needs_input_grad[0] and not ctx.needs_input_grad[1]:
                 # K is treated as symmetric (py:110-111)
                 grad_source = filt(g.contiguous(), ref.contiguous(), ctx.coeffs)
-            native = LatticeFilterGeneral.method is None and g.is_cuda and g.dim() == 2
+            # float32 only: the fused and the three-call position gradients are fp32 kernels.  In double the stack and the
+            # contraction below are torch in float64 around the native fp64 product on the derivative-tap lattice.
+            native = LatticeFilterGeneral.method is None and g.is_cuda and g.dim() == 2 and g.dtype == torch.float32
             if ctx.needs_input_grad[1] and native and LatticeFilterGeneral.fused_backward and Lattice.backward_fusable(L, d):
                 # the whole of py:113-123 in one native call: the stacked matrix is never stored (plx_apply_backward)
                 rc_ = ref if ref.is_contiguous() else carry_hint(ref.contiguous(), ref)
