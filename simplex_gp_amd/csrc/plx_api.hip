@@ -318,11 +318,37 @@ int64_t plx_device_bytes(const plx_lattice *L)
     return total;
 }
 
-static int check_apply(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
+// What every product call checks first: its arguments, a built lattice, a positive width.
+static int check_call(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
 {
     if (!L || !a || !b) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
     if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
     if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    return PLX_OK;
+}
+
+// The row-range and float64 products run on plain single-shard builds only.  `what`: the product with its verb, "row
+// ranges are" or "the float64 product is", as in
+//   "plx_apply_rows (source rows): sharded or merged lattice (row ranges are served by plain single-shard builds only)"
+//   "plx_apply_f64: this build replayed "reference_growth" (its splat and slice sides differ); the float64 product is
+//    not served on it"
+static int check_plain_build(const plx_lattice *L, const char *what, const char *who)
+{
+    if (L->n_shards != 1 || L->partial_cover) {
+        set_error("%s: sharded or merged lattice (%s served by plain single-shard builds only)", who, what);
+        return PLX_ERR_STATE;
+    }
+    if (L->replay.active) {
+        set_error("%s: this build replayed \"reference_growth\" (its splat and slice sides differ); %s not served on it", who,
+                  what);
+        return PLX_ERR_STATE;
+    }
+    return PLX_OK;
+}
+
+static int check_apply(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
+{
+    PLX_TRY(check_call(L, a, b, vd, who));
     if ((int64_t)L->m * values_stride(vd) >= (1ll << 31) ||
         (int64_t)(L->own_end - L->own_begin) * values_stride(vd) >= (1ll << 31)) {
         set_error("%s: m*vd or n*vd exceeds 2^31 elements; split the columns", who);
@@ -461,23 +487,13 @@ static int apply_common(plx_lattice *L, const float *d_src, int vd, float *d_out
 static int check_rows(const plx_lattice *L, const void *a, const void *b, int vd, int64_t begin, int64_t count,
                       const char *who)
 {
-    if (!L || !a || !b) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
-    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
-    if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    PLX_TRY(check_call(L, a, b, vd, who));
     if (count < 1 || begin < 0 || begin > L->n || count > L->n - begin) {
         set_error("%s: rows [%lld, %lld + %lld) are not a non-empty range inside [0, %lld)", who, (long long)begin,
                   (long long)begin, (long long)count, (long long)L->n);
         return PLX_ERR_INVALID;
     }
-    if (L->n_shards != 1 || L->partial_cover) {
-        set_error("%s: sharded or merged lattice (row ranges are served by plain single-shard builds only)", who);
-        return PLX_ERR_STATE;
-    }
-    if (L->replay.active) {
-        set_error("%s: this build replayed \"reference_growth\" (its splat and slice sides differ); row ranges are not "
-                  "served on it", who);
-        return PLX_ERR_STATE;
-    }
+    PLX_TRY(check_plain_build(L, "row ranges are", who));
     if ((int64_t)L->m * values_stride(vd) >= (1ll << 31) || count * values_stride(vd) >= (1ll << 31)) {
         set_error("%s: m*vd or rows*vd exceeds 2^31 elements; split the columns", who);
         return PLX_ERR_TOO_LARGE;
@@ -544,19 +560,9 @@ int plx_values_stride_f64(int vd) { return vd >= 1 ? values_stride_f64(vd) : -1;
 // Everything an fp64 call checks before any GPU work.  `a` / `b`: the call's two buffers of doubles.
 static int check_f64(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
 {
-    if (!L || !a || !b) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
-    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
-    if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    PLX_TRY(check_call(L, a, b, vd, who));
     if ((((uintptr_t)a | (uintptr_t)b) & 7) != 0) { set_error("%s: buffers of doubles must be 8-byte aligned", who); return PLX_ERR_INVALID; }
-    if (L->n_shards != 1 || L->partial_cover) {
-        set_error("%s: sharded or merged lattice (the float64 product is served by plain single-shard builds only)", who);
-        return PLX_ERR_STATE;
-    }
-    if (L->replay.active) {
-        set_error("%s: this build replayed \"reference_growth\" (its splat and slice sides differ); the float64 product is "
-                  "not served on it", who);
-        return PLX_ERR_STATE;
-    }
+    PLX_TRY(check_plain_build(L, "the float64 product is", who));
     if ((int64_t)L->m * values_stride_f64(vd) >= (1ll << 31) || (int64_t)L->n * values_stride_f64(vd) >= (1ll << 31)) {
         set_error("%s: m*vd or n*vd exceeds 2^31 elements; split the columns", who);
         return PLX_ERR_TOO_LARGE;

@@ -28,26 +28,13 @@
 
 namespace plx {
 
-__device__ __forceinline__ double2 d2_zero() { return make_double2(0.0, 0.0); }
-__device__ __forceinline__ void d2_fma(double2 &acc, double s, double2 x) { acc.x += s * x.x; acc.y += s * x.y; }
-
-template <class V> struct F64Ops;
-template <> struct F64Ops<double> {
-    static __device__ __forceinline__ double zero() { return 0.0; }
-    static __device__ __forceinline__ void fma(double &acc, double s, double x) { acc += s * x; }
-};
-template <> struct F64Ops<double2> {
-    static __device__ __forceinline__ double2 zero() { return d2_zero(); }
-    static __device__ __forceinline__ void fma(double2 &acc, double s, double2 x) { d2_fma(acc, s, x); }
-};
-
 // one chunk of a caller row: a 16-byte access where the rows are whole aligned chunks, else per double with the tail guarded
 template <bool VEC>
 __device__ __forceinline__ double2 f64_load_chunk(const double *__restrict__ src, size_t row, int vd, int ch)
 {
     const double *p = src + row * vd + 2 * ch;
     if constexpr (VEC) return *reinterpret_cast<const double2 *>(p);
-    double2 x = d2_zero();
+    double2 x = VecOps<double2>::zero();
     x.x = p[0];
     if (vd - 2 * ch > 1) x.y = p[1];
     return x;
@@ -68,9 +55,9 @@ template <bool VEC>
 __device__ __forceinline__ double2 f64_vertex_sum(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
                                                   const double *__restrict__ src, int vd, int ch)
 {
-    double2 acc = d2_zero();
+    double2 acc = VecOps<double2>::zero();
     for (int j = j0; j < j1; ++j)
-        d2_fma(acc, (double)w[j], f64_load_chunk<VEC>(src, (size_t)(row[j] & 0x7FFFFFFF), vd, ch));
+        VecOps<double2>::fma(acc, (double)w[j], f64_load_chunk<VEC>(src, (size_t)(row[j] & 0x7FFFFFFF), vd, ch));
     return acc;
 }
 
@@ -118,7 +105,7 @@ template <class V, int ORDER>
 __device__ __forceinline__ void f64_blur_item(const V *__restrict__ old, V *__restrict__ out, const int *__restrict__ nbr,
                                               int m, int64_t mstride, int rowlen, int order_rt, const double *c, int ntiles)
 {
-    using O = F64Ops<V>;
+    using O = VecOps<V>;
     const int tile = tile_index(ntiles);
     if (tile < 0) return;
     const uint32_t item = (uint32_t)tile * kBlock + threadIdx.x;      // (the entry point checks m * rowlen < 2^31)
@@ -178,14 +165,13 @@ __global__ __launch_bounds__(kBlock) void f64_blur_chunk_kernel(const double2 *_
 __device__ __forceinline__ double2 f64_point_sum(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
                                                  int d1, const double2 *__restrict__ values, int nch, int ch, double denom)
 {
-    double2 acc = d2_zero();
+    double2 acc = VecOps<double2>::zero();
     for (int r = 0; r < d1; ++r)
-        d2_fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)evid[(size_t)r * n + p] * nch + ch]);
+        VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)evid[(size_t)r * n + p] * nch + ch]);
     return make_double2(acc.x / denom, acc.y / denom);
 }
 
 // D1 > 0: d + 1 compiled in (all index / weight loads, then all gathers, then the ordered sum); 0: the run-time form
-constexpr int kF64MaxD1 = 20;
 template <int D1>
 __global__ __launch_bounds__(kBlock) void f64_slice_v1_kernel(const uint32_t *__restrict__ perm, const int *__restrict__ evid,
                                                               const float *__restrict__ ew, int n, int d1,
@@ -229,9 +215,9 @@ __global__ __launch_bounds__(kBlock) void f64_slice_chunk_kernel(const uint32_t 
         for (int r = 0; r < D1; ++r) v[r] = evid[(size_t)r * n + p];
 #pragma unroll
         for (int r = 0; r < D1; ++r) g[r] = values[(size_t)v[r] * nch + ch];
-        acc = d2_zero();
+        acc = VecOps<double2>::zero();
 #pragma unroll
-        for (int r = 0; r < D1; ++r) d2_fma(acc, (double)ew[(size_t)r * n + p], g[r]);
+        for (int r = 0; r < D1; ++r) VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], g[r]);
         acc = make_double2(acc.x / denom, acc.y / denom);
     } else {
         acc = f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom);
@@ -349,14 +335,10 @@ static void launch_slice_chunk_f64(plx_lattice *L, const double2 *v2, int vd, in
     const uint32_t *perm = L->perm.as<uint32_t>();
     const int *evid = L->evid.as<int>();
     const float *ew = L->ew.as<float>();
-    switch (d1 <= kF64MaxD1 ? d1 : 0) {
-#define PLX_CASE(D1) case D1: f64_slice_chunk_kernel<VEC, D1><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, v2, vd, nch, shift, denom, d_out); break;
-        PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9) PLX_CASE(10)
-        PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17) PLX_CASE(18)
-        PLX_CASE(19) PLX_CASE(20)
-#undef PLX_CASE
-    default: f64_slice_chunk_kernel<VEC, 0><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, v2, vd, nch, shift, denom, d_out); break;
-    }
+    dispatch_d1(d1, [&](auto D1) {
+        f64_slice_chunk_kernel<VEC, decltype(D1)::value><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, v2, vd,
+                                                                                      nch, shift, denom, d_out);
+    });
 }
 
 int slice_f64_impl(plx_lattice *L, const double *d_values, int vd, double *d_out, hipStream_t stream)
@@ -371,14 +353,10 @@ int slice_f64_impl(plx_lattice *L, const double *d_values, int vd, double *d_out
     if (vd == 1) {
         L->kn_f64_slice = "f64_slice_v1_kernel";
         const int grid = ceil_div(n, kBlock);
-        switch (d1 <= kF64MaxD1 ? d1 : 0) {
-#define PLX_CASE(D1) case D1: f64_slice_v1_kernel<D1><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, d_values, denom, d_out); break;
-            PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9) PLX_CASE(10)
-            PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17) PLX_CASE(18)
-            PLX_CASE(19) PLX_CASE(20)
-#undef PLX_CASE
-        default: f64_slice_v1_kernel<0><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, d_values, denom, d_out); break;
-        }
+        dispatch_d1(d1, [&](auto D1) {
+            f64_slice_v1_kernel<decltype(D1)::value><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, d_values,
+                                                                                  denom, d_out);
+        });
     } else if (nch <= kF64ChunkMax) {
         L->kn_f64_slice = "f64_slice_chunk_kernel";
         if (vec) launch_slice_chunk_f64<true>(L, v2, vd, nch, denom, d_out, stream);

@@ -1,5 +1,6 @@
-// plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files
-// (plx_splat.hip, plx_blur.hip, plx_slice.hip).  Not part of the C ABI.
+// plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
+// plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip).  Not part of
+// the C ABI.
 //
 // Reference: cpp/permutohedral.h ("h") splat value accumulation h:478-479,
 // blur h:513-572, slice h:497-510.  The reference's CUDA path does the splat
@@ -61,7 +62,8 @@ __device__ __forceinline__ float4 f4_shfl_up(float4 a, int off)
     return make_float4(__shfl_up(a.x, off), __shfl_up(a.y, off), __shfl_up(a.z, off), __shfl_up(a.w, off));
 }
 
-
+// One scalar or one 16-byte chunk of a value row.  The double forms (the float64 product) have zero and fma only:
+// fma(acc, s, x) is acc += s * x per element.
 template <class V> struct VecOps;
 template <> struct VecOps<float> {
     static __device__ __forceinline__ float zero() { return 0.f; }
@@ -77,6 +79,28 @@ template <> struct VecOps<float4> {
     static __device__ __forceinline__ float4 sel(bool c, float4 a, float4 b) { return f4_sel(c, a, b); }
     static __device__ __forceinline__ float4 shfl_up(float4 a, int off) { return f4_shfl_up(a, off); }
 };
+template <> struct VecOps<double> {
+    static __device__ __forceinline__ double zero() { return 0.0; }
+    static __device__ __forceinline__ void fma(double &acc, double s, double x) { acc += s * x; }
+};
+template <> struct VecOps<double2> {
+    static __device__ __forceinline__ double2 zero() { return make_double2(0.0, 0.0); }
+    static __device__ __forceinline__ void fma(double2 &acc, double s, double2 x) { acc.x += s * x.x; acc.y += s * x.y; }
+};
 
+// The gather slices of plx_rows.hip and plx_f64.hip have d + 1 compiled in up to kGatherMaxD1:
+// f(std::integral_constant<int, D1>) with D1 = d1 for 2..20, else 0 (the run-time form).
+constexpr int kGatherMaxD1 = 20;
+template <class F> static inline void dispatch_d1(int d1, F &&f)
+{
+    switch (d1 <= kGatherMaxD1 ? d1 : 0) {
+#define PLX_CASE(D1) case D1: f(std::integral_constant<int, D1>{}); break;
+        PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9) PLX_CASE(10)
+        PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17) PLX_CASE(18)
+        PLX_CASE(19) PLX_CASE(20)
+#undef PLX_CASE
+    default: f(std::integral_constant<int, 0>{}); break;
+    }
+}
 
 }  // namespace plx

@@ -297,7 +297,6 @@ __global__ __launch_bounds__(kBlock) void rows_slice_v1_kernel(const int *__rest
 }
 
 // D1 > 0: d + 1 compiled in (all index / weight loads, then all gathers, then the ordered sum); 0: the run-time form
-constexpr int kRowsMaxD1 = 20;
 template <bool VEC, int D1>
 __global__ __launch_bounds__(kBlock) void rows_slice_chunk_kernel(const int *__restrict__ pos, const int *__restrict__ prow,
                                                                   const int *__restrict__ evid, const float *__restrict__ ew,
@@ -397,14 +396,11 @@ static void launch_slice_chunk(plx_lattice *L, const plx_lattice::RowsRange *r, 
     const int *pos = r->pos.as<int>(), *prow = r->prow.as<int>();
     const int *evid = L->evid.as<int>();
     const float *ew = L->ew.as<float>();
-    switch (d1 <= kRowsMaxD1 ? d1 : 0) {
-#define PLX_CASE(D1) case D1: rows_slice_chunk_kernel<VEC, D1><<<grid, kBlock, 0, stream>>>(pos, prow, evid, ew, n, d1, count, v4, vd, nch, shift, rden, d_out); break;
-        PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8) PLX_CASE(9) PLX_CASE(10)
-        PLX_CASE(11) PLX_CASE(12) PLX_CASE(13) PLX_CASE(14) PLX_CASE(15) PLX_CASE(16) PLX_CASE(17) PLX_CASE(18)
-        PLX_CASE(19) PLX_CASE(20)
-#undef PLX_CASE
-    default: rows_slice_chunk_kernel<VEC, 0><<<grid, kBlock, 0, stream>>>(pos, prow, evid, ew, n, d1, count, v4, vd, nch, shift, rden, d_out); break;
-    }
+    dispatch_d1(d1, [&](auto D1) {
+        rows_slice_chunk_kernel<VEC, decltype(D1)::value><<<grid, kBlock, 0, stream>>>(pos, prow, evid, ew, n, d1,
+                                                                                       count, v4, vd, nch, shift, rden,
+                                                                                       d_out);
+    });
 }
 
 int slice_rows_impl(plx_lattice *L, const float *d_values, int vd, int64_t begin, int64_t count, float *d_out,

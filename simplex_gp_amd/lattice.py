@@ -239,16 +239,20 @@ class Lattice:
         nv.check(nv.lib().plx_build_times(self._h, buf), "plx_build_times")
         return dict(zip(("embed", "insert", "number", "ids", "neighbours", "csr"), list(buf)))
 
-    def stage_kernels(self, vd=None):
-        """Kernels launched by the last splat / blur / slice on this lattice: {"splat": [...], "blur_axis": [...],
-        "slice": [...]} (names as rocprofv3 shows them, without template arguments)."""
-        buf = ctypes.create_string_buffer(512)
-        nv.check(nv.lib().plx_last_kernels(self._h, buf, 512), "plx_last_kernels")
+    def _last_kernels(self, fn, cap):
+        """What the C call `fn` reports, "a=x+y;b=z", as {"a": ["x", "y"], "b": ["z"]}."""
+        buf = ctypes.create_string_buffer(cap)
+        nv.check(getattr(nv.lib(), fn)(self._h, buf, cap), fn)
         out = {}
         for part in buf.value.decode().split(";"):
             k, _, names = part.partition("=")
             out[k] = [x for x in names.split("+") if x]
         return out
+
+    def stage_kernels(self, vd=None):
+        """Kernels launched by the last splat / blur / slice on this lattice: {"splat": [...], "blur_axis": [...],
+        "slice": [...]} (names as rocprofv3 shows them, without template arguments)."""
+        return self._last_kernels("plx_last_kernels", 512)
 
     def prepare(self, vd=1):
         """Build now every table an MVM with vd columns will read (otherwise the first such MVM builds them)."""
@@ -402,13 +406,7 @@ class Lattice:
     def f64_kernels(self):
         """Kernels launched by the last float64 splat / blur / slice (or apply) on this lattice: {"splat": [...],
         "blur_axis": [...], "slice": [...]}; stage_kernels() goes on naming the fp32 stages."""
-        buf = ctypes.create_string_buffer(256)
-        nv.check(nv.lib().plx_last_f64_kernels(self._h, buf, 256), "plx_last_f64_kernels")
-        out = {}
-        for part in buf.value.decode().split(";"):
-            k, _, names = part.partition("=")
-            out[k] = [x for x in names.split("+") if x]
-        return out
+        return self._last_kernels("plx_last_f64_kernels", 256)
 
     # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
     def _rows(self, begin, count):
@@ -468,13 +466,7 @@ class Lattice:
     def rows_kernels(self):
         """Kernels launched by the last splat_rows / slice_rows (or apply_rows) on this lattice: {"splat": [...],
         "slice": [...]}; the blur of apply_rows reports through stage_kernels()."""
-        buf = ctypes.create_string_buffer(256)
-        nv.check(nv.lib().plx_last_rows_kernels(self._h, buf, 256), "plx_last_rows_kernels")
-        out = {}
-        for part in buf.value.decode().split(";"):
-            k, _, names = part.partition("=")
-            out[k] = [x for x in names.split("+") if x]
-        return out
+        return self._last_kernels("plx_last_rows_kernels", 256)
 
     def accepts_rows(self):
         """True when the rows calls serve this lattice: a plain single-shard build without the "reference_growth" replay."""

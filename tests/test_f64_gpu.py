@@ -64,13 +64,14 @@ LATTICES = {
     "isolated": ("isolated", 1000, 3, 2),
     "dup": ("dup", 2000, 8, 2),
     "grid": ("grid", 2000, 3, 3),
+    "d24": ("gauss1", 600, 24, 1),               # d + 1 > 20: the slices' run-time form; its own two cases, not the rotation
 }
 VDS = (1, 2, 3, 4, 11, 12, 101, 520)
 
 
 def _cases():
     out = []
-    for i, lname in enumerate(LATTICES):
+    for i, lname in enumerate(l for l in LATTICES if l != "d24"):
         for j in range(3):                                   # three widths per lattice, rotating through all of them
             vd = VDS[(3 * i + j) % len(VDS)]
             out.append((lname, vd, (i + j) % 2 == 0))
@@ -81,6 +82,7 @@ def _cases():
     for vd in (1, 12, 520):                                  # every family on the sparse high-dimensional lattice
         if ("d18", vd, True) not in out:
             out.append(("d18", vd, True))
+    out += [("d24", 1, True), ("d24", 12, False)]
     return out
 
 

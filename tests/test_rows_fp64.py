@@ -68,6 +68,7 @@ LATTICES = {
     "d18": ("gauss1", 3000, 18, 1),        # sparse: m = n (d + 1), every corner its own vertex
     "coarse": ("gauss0.3", 20000, 3, 1),   # coarse: thousands of corners per vertex row
     "d8o1": ("gauss3", 4000, 8, 1),
+    "d24": ("gauss1", 600, 24, 1),         # d + 1 > 20: the chunk slice's run-time form; its own two cases, not the grid
 }
 VDS = (1, 3, 4, 11, 12, 101, 130, 512, 520)
 RANGES = ("head0.8", "head0.8T", "head0.5", "head0.5T", "one", "oneT", "equal", "overlap", "full")
@@ -89,7 +90,7 @@ def ranges(name, n):
 
 def _cases():
     out = []
-    for i, lname in enumerate(LATTICES):
+    for i, lname in enumerate(l for l in LATTICES if l != "d24"):
         for j, vd in enumerate(VDS):
             out.append((lname, vd, RANGES[(2 * i + j) % len(RANGES)], (i + j) % 2 == 0))
     for j, vd in enumerate((1, 11, 101)):                  # every range at one lattice, a width of each narrow kind
@@ -97,6 +98,7 @@ def _cases():
             case = ("d8", vd, rname, (j + k) % 2 == 1)
             if case not in out:
                 out.append(case)
+    out += [("d24", 1, "overlap", True), ("d24", 12, "overlap", False)]
     return out
 
 
