@@ -414,9 +414,13 @@ int plx_cg_direction(float *d_p, const float *d_r, const float *d_beta, int64_t 
  * 16 MB; < 0 for sizes outside the limits), so nothing is allocated and the calls are graph-capturable.  Deterministic:
  * no float atomics (a split j range is summed slice by slice in a fixed order).  Every argument is checked before any
  * GPU work (PLX_ERR_INVALID, PLX_ERR_DIM for d).
+ * plx_exact_splits: the number of slices the j range of that call is cut into (1: written directly, no workspace
+ * used; > 1: slabs [splits][n1][t or d] in d_work, summed in slice order); -1 where plx_exact_work_bytes refuses.  A
+ * host function, no device needed: a test knows which path a call takes without restating the rule.
  */
 enum { PLX_PROFILE_RBF = 0, PLX_PROFILE_MATERN12 = 1, PLX_PROFILE_MATERN32 = 2, PLX_PROFILE_MATERN52 = 3 };
 int64_t plx_exact_work_bytes(int64_t n1, int64_t n2, int d, int t);
+int plx_exact_splits(int64_t n1, int64_t n2, int d, int t);
 int plx_exact_mvm(const float *d_x1, int64_t n1, const float *d_x2, int64_t n2, int d, int profile,
                   const float *d_v, int t, float *d_out, void *d_work, int64_t work_bytes, void *stream);
 int plx_exact_grad(const float *d_x1, int64_t n1, const float *d_x2, int64_t n2, int d, int profile,

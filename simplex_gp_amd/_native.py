@@ -94,6 +94,7 @@ _SIGNATURES = {
     "plx_cg_update": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "plx_cg_direction": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "plx_exact_work_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "plx_exact_splits": (_i32, [_i64, _i64, _i32, _i32]),
     "plx_exact_mvm": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "plx_exact_grad": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
     "plx_pcg_work_floats": (_i64, [_i64, _i32, _i32]),

@@ -364,7 +364,7 @@ static int ex_run(bool grad, const float *x1, int64_t n1, const float *x2, int64
                   const float *v, int t, float *dst, void *work, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    const int splits = ex_splits(n1, n2, d, t);
+    const int splits = plx_exact_splits(n1, n2, d, t);      // the query the header documents: it cannot drift from the launch
     float *target = splits > 1 ? reinterpret_cast<float *>(work) : dst;
     switch (profile) {
     case PLX_PROFILE_RBF: ex_dispatch_dp<PLX_PROFILE_RBF>(grad, x1, n1, x2, n2, d, g, v, t, target, splits, s); break;
@@ -389,6 +389,12 @@ extern "C" int64_t plx_exact_work_bytes(int64_t n1, int64_t n2, int d, int t)
 {
     if (n1 < 1 || n2 < 1 || n1 >= kExMaxRows || n2 >= kExMaxRows || d < 1 || d > PLX_MAX_DIM || t < 1) return -1;
     return 4 * ex_work_floats(n1, n2, d, t);
+}
+
+extern "C" int plx_exact_splits(int64_t n1, int64_t n2, int d, int t)
+{
+    if (plx_exact_work_bytes(n1, n2, d, t) < 0) return -1;
+    return ex_splits(n1, n2, d, t);
 }
 
 extern "C" int plx_exact_mvm(const float *d_x1, int64_t n1, const float *d_x2, int64_t n2, int d, int profile, const float *d_v,

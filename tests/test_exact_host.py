@@ -24,7 +24,7 @@ def p():
 
 
 def test_exact_symbols_and_version(lib):
-    for name in ("plx_exact_work_bytes", "plx_exact_mvm", "plx_exact_grad"):
+    for name in ("plx_exact_work_bytes", "plx_exact_splits", "plx_exact_mvm", "plx_exact_grad"):
         assert name in _native.declared_symbols() and name in _native._SIGNATURES
     assert lib.plx_version().decode().startswith("libplx 0.9.")
     assert _native.ABI_VERSION == (0, 9)
@@ -88,6 +88,25 @@ def test_exact_work_bytes_limits_and_monotone(lib):
         w = [lib.plx_exact_work_bytes(n1, 5000, 8, t) for t in ts]
         assert w == sorted(w), (n1, w)
     assert max(lib.plx_exact_work_bytes(n, n, 32, 4096) for n in sizes_n) <= 16 << 20
+
+
+def test_exact_splits_limits_and_workspace(lib):
+    """the split count is refused exactly where the workspace bound is, and its slabs (n1 max(d, t) floats each) fit the
+    workspace at every size"""
+    assert lib.plx_exact_splits(0, 10, 3, 1) == -1 and lib.plx_exact_splits(10, 0, 3, 1) == -1
+    assert lib.plx_exact_splits(10, 10, 0, 1) == -1 and lib.plx_exact_splits(10, 10, 33, 1) == -1
+    assert lib.plx_exact_splits(10, 10, 3, 0) == -1 and lib.plx_exact_splits(1 << 31, 10, 3, 1) == -1
+    assert lib.plx_exact_splits(10, 1 << 31, 3, 1) == -1 and lib.plx_exact_splits(-1, 10, 3, 1) == -1
+    assert lib.plx_exact_splits(4096, 4096, 3, 1) == 8 and lib.plx_exact_splits(8, 200_000, 8, 11) == 390
+    assert lib.plx_exact_splits(64, 511, 3, 1) == 1 and lib.plx_exact_splits(1_000_000, 1_000_000, 3, 1) == 1
+    sizes = [1, 7, 8, 255, 256, 257, 3001, 65536, 262_145, 524_288, 524_289, 2_049_280, (1 << 31) - 1]
+    for n1 in sizes:
+        for n2 in sizes:
+            for d, t in ((1, 1), (3, 1), (32, 1), (3, 11), (8, 64), (18, 257), (32, 4096), (1, 5_000_000)):
+                s = lib.plx_exact_splits(n1, n2, d, t)
+                assert 1 <= s <= 1024 and (s == 1 or s <= max(1, n2 // 512)), (n1, n2, d, t, s)
+                if s > 1:
+                    assert 4 * s * n1 * max(d, t) <= lib.plx_exact_work_bytes(n1, n2, d, t), (n1, n2, d, t, s)
 
 
 def test_exact_matmul_has_no_cpu_path():
