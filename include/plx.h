@@ -295,6 +295,43 @@ int plx_apply_f64(plx_lattice *lat, const double *d_src, int vd, double *d_out, 
 int plx_last_f64_kernels(const plx_lattice *lat, char *buf, int cap);
 
 /*
+ * The float64 rectangular product K(A, B) v by row range (callers detect it by symbol; the version string is unchanged):
+ * plx_splat_rows / plx_slice_rows / plx_apply_rows with the arithmetic of the float64 product -- the fp32 weights and taps
+ * converted exactly, every sum in double, one division by 1 + 2^-d in double.
+ *   plx_splat_rows_f64  d_values[m][plx_values_stride_f64(vd)] = S^T restricted to the caller's rows [row_begin, row_begin +
+ *                       row_count): d_src is [row_count][vd].  Every vertex row is written (vertices the range does not
+ *                       touch get 0); there is no zero-fill pass.
+ *   plx_slice_rows_f64  d_out[row_count][vd] = rows [row_begin, row_begin + row_count) of S d_values / (1 + 2^-d).
+ *   plx_apply_rows_f64  splat_rows_f64 -> the blur of plx_apply_f64 -> slice_rows_f64 on the float64 workspace that
+ *                       plx_apply_f64 owns (the same two value planes, no second workspace).
+ *   plx_last_rows_f64_kernels  "splat=...;slice=..." of the last fp64 rows call (the blur inside plx_apply_rows_f64 reports
+ *                       through plx_last_f64_kernels).
+ * Rows are ALWAYS in the caller's order.  d_src / d_out need 8-byte alignment only; d_values is 16-byte aligned when
+ * vd > 1 (PLX_ERR_INVALID otherwise).
+ * Scope and refusals are those of plx_apply_rows and plx_apply_f64 together: a lattice that is not built, a sharded or
+ * merged lattice and a build that replayed "reference_growth" return PLX_ERR_STATE; NULL pointers, vd < 1, a count < 1, a
+ * range outside [0, n), misaligned buffers are PLX_ERR_INVALID; m * stride and row_count * stride stay under 2^31 elements
+ * (PLX_ERR_TOO_LARGE).  Every argument is checked before any GPU work.
+ * Tables: the range tables are those of the fp32 rows calls -- they hold no values.  The four slots and their least-
+ * recently-used recycling are shared between the precisions: a range that an fp32 call built serves the fp64 call, and the
+ * reverse.  Under stream capture a call that would have to build a range table or grow the workspace returns
+ * PLX_ERR_STATE; from the second call of a (range, width) on, a call neither allocates nor synchronises (plx_device_bytes
+ * does not move) and is graph-capturable.
+ * Bit contract: every sum is taken in the order of plx_apply_f64 (a range's corners are a stable compaction of the vertex-
+ * sorted corners; a dropped term is fma(w, 0, acc) = acc), so for every pair of ranges plx_apply_rows_f64 equals AS VALUES
+ * (-0.0 counted equal to +0.0) rows [out_begin, out_begin + out_count) of plx_apply_f64 applied to the n-row matrix that
+ * holds d_src in the source rows and zeros elsewhere; the full range on both ends equals plx_apply_f64 in the same way, and
+ * the staged calls give the bits of plx_apply_rows_f64.  No float atomics: two calls with the same arguments are bit-equal.
+ */
+int plx_splat_rows_f64(plx_lattice *lat, const double *d_src, int64_t row_begin, int64_t row_count, int vd,
+                       double *d_values, void *stream);
+int plx_slice_rows_f64(plx_lattice *lat, const double *d_values, int vd, int64_t row_begin, int64_t row_count,
+                       double *d_out, void *stream);
+int plx_apply_rows_f64(plx_lattice *lat, const double *d_src, int64_t src_begin, int64_t src_count, int vd,
+                       double *d_out, int64_t out_begin, int64_t out_count, void *stream);
+int plx_last_rows_f64_kernels(const plx_lattice *lat, char *buf, int cap);   /* "splat=...;slice=..." */
+
+/*
  * The reference's one-shot call (cpp:6-10 -> h:259-340): build a lattice for
  * d_ref, apply it to d_src, leave nothing behind.  `scratch` may be NULL or a
  * lattice object whose buffers are reused (avoids hipMalloc in steady state; it

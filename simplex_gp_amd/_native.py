@@ -67,6 +67,10 @@ _SIGNATURES = {
     "plx_slice_f64": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "plx_apply_f64": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "plx_last_f64_kernels": (_i32, [_vp, ctypes.c_char_p, _i32]),
+    "plx_splat_rows_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "plx_slice_rows_f64": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _vp]),
+    "plx_apply_rows_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
+    "plx_last_rows_f64_kernels": (_i32, [_vp, ctypes.c_char_p, _i32]),
     "plx_filter": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _f32p, _i32, _vp, _vp]),
     "plx_coldot": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "plx_coldot_work_floats": (_i64, [_i32]),

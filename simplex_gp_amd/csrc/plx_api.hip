@@ -483,22 +483,36 @@ static int apply_common(plx_lattice *L, const float *d_src, int vd, float *d_out
 
 // ---- the rectangular product: splat / slice by row range (kernels and tables: plx_rows.hip) ----------------------------
 
-// Everything a rows call checks before any GPU work.  `a` / `b`: the call's two buffers.
-static int check_rows(const plx_lattice *L, const void *a, const void *b, int vd, int64_t begin, int64_t count,
-                      const char *who)
+// The two checks the rows calls and the fp64 calls share.  A range of caller rows: non-empty, inside [0, n).
+static int check_range(const plx_lattice *L, int64_t begin, int64_t count, const char *who)
 {
-    PLX_TRY(check_call(L, a, b, vd, who));
     if (count < 1 || begin < 0 || begin > L->n || count > L->n - begin) {
         set_error("%s: rows [%lld, %lld + %lld) are not a non-empty range inside [0, %lld)", who, (long long)begin,
                   (long long)begin, (long long)count, (long long)L->n);
         return PLX_ERR_INVALID;
     }
-    PLX_TRY(check_plain_build(L, "row ranges are", who));
-    if ((int64_t)L->m * values_stride(vd) >= (1ll << 31) || count * values_stride(vd) >= (1ll << 31)) {
-        set_error("%s: m*vd or rows*vd exceeds 2^31 elements; split the columns", who);
+    return PLX_OK;
+}
+
+// The 2^31 element limits of the gather kernels: m vertex rows and `rows` caller rows (named `rows_name` in the message) of
+// `stride` elements each.
+static int check_size(const plx_lattice *L, int stride, int64_t rows, const char *rows_name, const char *who)
+{
+    if ((int64_t)L->m * stride >= (1ll << 31) || rows * stride >= (1ll << 31)) {
+        set_error("%s: m*vd or %s*vd exceeds 2^31 elements; split the columns", who, rows_name);
         return PLX_ERR_TOO_LARGE;
     }
     return PLX_OK;
+}
+
+// Everything a rows call checks before any GPU work.  `a` / `b`: the call's two buffers.
+static int check_rows(const plx_lattice *L, const void *a, const void *b, int vd, int64_t begin, int64_t count,
+                      const char *who)
+{
+    PLX_TRY(check_call(L, a, b, vd, who));
+    PLX_TRY(check_range(L, begin, count, who));
+    PLX_TRY(check_plain_build(L, "row ranges are", who));
+    return check_size(L, values_stride(vd), count, "rows", who);
 }
 
 static int check_values_aligned(const void *d_values, int vd, const char *who)
@@ -557,17 +571,19 @@ int plx_last_rows_kernels(const plx_lattice *L, char *buf, int cap)
 
 int plx_values_stride_f64(int vd) { return vd >= 1 ? values_stride_f64(vd) : -1; }
 
+static int check_doubles_aligned(const void *a, const void *b, const char *who)
+{
+    if ((((uintptr_t)a | (uintptr_t)b) & 7) != 0) { set_error("%s: buffers of doubles must be 8-byte aligned", who); return PLX_ERR_INVALID; }
+    return PLX_OK;
+}
+
 // Everything an fp64 call checks before any GPU work.  `a` / `b`: the call's two buffers of doubles.
 static int check_f64(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
 {
     PLX_TRY(check_call(L, a, b, vd, who));
-    if ((((uintptr_t)a | (uintptr_t)b) & 7) != 0) { set_error("%s: buffers of doubles must be 8-byte aligned", who); return PLX_ERR_INVALID; }
+    PLX_TRY(check_doubles_aligned(a, b, who));
     PLX_TRY(check_plain_build(L, "the float64 product is", who));
-    if ((int64_t)L->m * values_stride_f64(vd) >= (1ll << 31) || (int64_t)L->n * values_stride_f64(vd) >= (1ll << 31)) {
-        set_error("%s: m*vd or n*vd exceeds 2^31 elements; split the columns", who);
-        return PLX_ERR_TOO_LARGE;
-    }
-    return PLX_OK;
+    return check_size(L, values_stride_f64(vd), L->n, "n", who);
 }
 
 int plx_splat_f64(plx_lattice *L, const double *d_src, int vd, double *d_values, void *stream)
@@ -618,6 +634,62 @@ int plx_last_f64_kernels(const plx_lattice *L, char *buf, int cap)
 {
     if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
     snprintf(buf, (size_t)cap, "splat=%s;blur_axis=%s;slice=%s", L->kn_f64_splat, L->kn_f64_blur, L->kn_f64_slice);
+    return PLX_OK;
+}
+
+// ---- the float64 rectangular product (kernels: plx_rows_f64.hip; tables: plx_rows.hip; blur: plx_f64.hip) --------------
+
+// check_rows and check_f64 in one: the checks of both, each once.
+static int check_rows_f64(const plx_lattice *L, const void *a, const void *b, int vd, int64_t begin, int64_t count,
+                          const char *who)
+{
+    PLX_TRY(check_call(L, a, b, vd, who));
+    PLX_TRY(check_doubles_aligned(a, b, who));
+    PLX_TRY(check_range(L, begin, count, who));
+    PLX_TRY(check_plain_build(L, "float64 row ranges are", who));
+    return check_size(L, values_stride_f64(vd), count, "rows", who);
+}
+
+int plx_splat_rows_f64(plx_lattice *L, const double *d_src, int64_t row_begin, int64_t row_count, int vd, double *d_values,
+                       void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_rows_f64(L, d_src, d_values, vd, row_begin, row_count, "plx_splat_rows_f64"));
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_splat_rows_f64"));
+    DeviceGuard g(L->device);
+    return splat_rows_f64_impl(L, d_src, row_begin, row_count, vd, d_values, (hipStream_t)stream);
+}
+
+int plx_slice_rows_f64(plx_lattice *L, const double *d_values, int vd, int64_t row_begin, int64_t row_count, double *d_out,
+                       void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_rows_f64(L, d_values, d_out, vd, row_begin, row_count, "plx_slice_rows_f64"));
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_slice_rows_f64"));
+    DeviceGuard g(L->device);
+    return slice_rows_f64_impl(L, d_values, vd, row_begin, row_count, d_out, (hipStream_t)stream);
+}
+
+int plx_apply_rows_f64(plx_lattice *L, const double *d_src, int64_t src_begin, int64_t src_count, int vd, double *d_out,
+                       int64_t out_begin, int64_t out_count, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_rows_f64(L, d_src, d_out, vd, src_begin, src_count, "plx_apply_rows_f64 (source rows)"));
+    PLX_TRY(check_rows_f64(L, d_src, d_out, vd, out_begin, out_count, "plx_apply_rows_f64 (output rows)"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    PLX_TRY(ensure(L->val64_a, (size_t)L->m * values_stride_f64(vd) * 8));      // the workspace of plx_apply_f64
+    PLX_TRY(ensure(L->val64_b, (size_t)L->m * values_stride_f64(vd) * 8));
+    PLX_TRY(splat_rows_f64_impl(L, d_src, src_begin, src_count, vd, L->val64_a.as<double>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), vd, &in_b, s));
+    return slice_rows_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, out_begin, out_count, d_out, s);
+}
+
+int plx_last_rows_f64_kernels(const plx_lattice *L, char *buf, int cap)
+{
+    if (!L || !buf || cap < 1) { set_error("plx_last_rows_f64_kernels: NULL argument or no room"); return PLX_ERR_INVALID; }
+    snprintf(buf, (size_t)cap, "splat=%s;slice=%s", L->kn_rows64_splat, L->kn_rows64_slice);
     return PLX_OK;
 }
 

@@ -28,39 +28,7 @@
 
 namespace plx {
 
-// one chunk of a caller row: a 16-byte access where the rows are whole aligned chunks, else per double with the tail guarded
-template <bool VEC>
-__device__ __forceinline__ double2 f64_load_chunk(const double *__restrict__ src, size_t row, int vd, int ch)
-{
-    const double *p = src + row * vd + 2 * ch;
-    if constexpr (VEC) return *reinterpret_cast<const double2 *>(p);
-    double2 x = VecOps<double2>::zero();
-    x.x = p[0];
-    if (vd - 2 * ch > 1) x.y = p[1];
-    return x;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void f64_store_chunk(double *__restrict__ out, size_t row, int vd, int ch, double2 a)
-{
-    double *o = out + row * vd + 2 * ch;
-    if constexpr (VEC) { *reinterpret_cast<double2 *>(o) = a; return; }
-    o[0] = a.x;
-    if (vd - 2 * ch > 1) o[1] = a.y;
-}
-
-// ---- splat ---------------------------------------------------------------------------------------------------------
-// corners [j0, j1) of one vertex; csr_row carries the segment-head flag of the fp32 scan in its sign bit
-template <bool VEC>
-__device__ __forceinline__ double2 f64_vertex_sum(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
-                                                  const double *__restrict__ src, int vd, int ch)
-{
-    double2 acc = VecOps<double2>::zero();
-    for (int j = j0; j < j1; ++j)
-        VecOps<double2>::fma(acc, (double)w[j], f64_load_chunk<VEC>(src, (size_t)(row[j] & 0x7FFFFFFF), vd, ch));
-    return acc;
-}
-
+// ---- splat (f64_load_chunk / f64_store_chunk / f64_vertex_sum / f64_point_sum: plx_kernels.h) ----------------------------
 __global__ __launch_bounds__(kBlock) void f64_splat_v1_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
                                                               const float *__restrict__ w, const double *__restrict__ src,
                                                               int m, double *__restrict__ values)
@@ -161,16 +129,6 @@ __global__ __launch_bounds__(kBlock) void f64_blur_chunk_kernel(const double2 *_
 }
 
 // ---- slice ---------------------------------------------------------------------------------------------------------
-// sum_r w_r values[v_r][ch] in corner order, then ONE division by 1 + 2^-d
-__device__ __forceinline__ double2 f64_point_sum(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
-                                                 int d1, const double2 *__restrict__ values, int nch, int ch, double denom)
-{
-    double2 acc = VecOps<double2>::zero();
-    for (int r = 0; r < d1; ++r)
-        VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)evid[(size_t)r * n + p] * nch + ch]);
-    return make_double2(acc.x / denom, acc.y / denom);
-}
-
 // D1 > 0: d + 1 compiled in (all index / weight loads, then all gathers, then the ordered sum); 0: the run-time form
 template <int D1>
 __global__ __launch_bounds__(kBlock) void f64_slice_v1_kernel(const uint32_t *__restrict__ perm, const int *__restrict__ evid,
@@ -239,17 +197,7 @@ __global__ __launch_bounds__(kBlock) void f64_slice_wide_kernel(const uint32_t *
         f64_store_chunk<VEC>(out, row, vd, ch, f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom));
 }
 
-// ---- launch side ---------------------------------------------------------------------------------------------------
-constexpr int kF64ChunkMax = 64;      // chunks one lane group can cover: a group never spans two waves
-
-static inline bool f64_vec_ok(const void *p, int vd) { return (vd & 1) == 0 && ((uintptr_t)p & 15) == 0; }
-static inline int f64_group_shift(int nch)
-{
-    int s = 0;
-    while ((1 << s) < nch) ++s;
-    return s;
-}
-
+// ---- launch side (kF64ChunkMax / f64_vec_ok / f64_group_shift: plx_kernels.h) -----------------------------------------------
 // The vertex-sorted corners of the current build and the first corner of every vertex (ensure_csr + its row pointer):
 // built by the first fp64 splat after a build, kept until the next one.
 static int ensure_f64_tables(plx_lattice *L, hipStream_t stream)

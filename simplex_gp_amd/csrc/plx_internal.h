@@ -292,6 +292,7 @@ struct plx_lattice {
     plx::DevBuf val64_a, val64_b;             // double [m][plx_values_stride_f64(vd)]
     uint64_t f64_gen = 0;                     // build_gen of that build (0: none)
     const char *kn_f64_splat = "", *kn_f64_blur = "", *kn_f64_slice = "";   // kernels of the last fp64 call (plx_last_f64_kernels)
+    const char *kn_rows64_splat = "", *kn_rows64_slice = "";   // kernels of the last fp64 rows call (plx_last_rows_f64_kernels)
 
     int32_t *h_pinned = nullptr;   // pinned host staging (exports)
     int *h_mail = nullptr;         // mailbox of read_back: coherent pinned host memory, word 0 = sequence number, then up to 62 values
@@ -370,6 +371,16 @@ int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t c
                     hipStream_t stream);
 int slice_rows_impl(plx_lattice *L, const float *d_values, int vd, int64_t begin, int64_t count, float *d_out,
                     hipStream_t stream);
+// ... and the range tables, which hold no values and serve both precisions: the slot of a range (the one that holds it,
+// else an empty one, else the least recently used) and its splat / slice side, built on first use
+plx_lattice::RowsRange *range_slot(plx_lattice *L, int64_t begin, int64_t count);
+int ensure_rows_splat(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream);
+int ensure_rows_slice(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream);
+// plx_rows_f64.hip: the same two stages on buffers of doubles, over the same tables
+int splat_rows_f64_impl(plx_lattice *L, const double *d_src, int64_t begin, int64_t count, int vd, double *d_values,
+                        hipStream_t stream);
+int slice_rows_f64_impl(plx_lattice *L, const double *d_values, int vd, int64_t begin, int64_t count, double *d_out,
+                        hipStream_t stream);
 // plx_f64.hip: the three stages in float64 on caller buffers of doubles (arguments checked by the entry points)
 int splat_f64_impl(plx_lattice *L, const double *d_src, int vd, double *d_values, hipStream_t stream);
 int blur_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);

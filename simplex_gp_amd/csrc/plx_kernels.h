@@ -1,6 +1,6 @@
 // plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
-// plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip).  Not part of
-// the C ABI.
+// plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip,
+// plx_rows_f64.hip).  Not part of the C ABI.
 //
 // Reference: cpp/permutohedral.h ("h") splat value accumulation h:478-479,
 // blur h:513-572, slice h:497-510.  The reference's CUDA path does the splat
@@ -88,7 +88,61 @@ template <> struct VecOps<double2> {
     static __device__ __forceinline__ void fma(double2 &acc, double s, double2 x) { acc.x += s * x.x; acc.y += s * x.y; }
 };
 
-// The gather slices of plx_rows.hip and plx_f64.hip have d + 1 compiled in up to kGatherMaxD1:
+// ---- the float64 gathers (plx_f64.hip, plx_rows_f64.hip): the pieces both files form their sums from, so that the same
+// terms in the same order give the same bits in both ----
+// one chunk of a caller row: a 16-byte access where the rows are whole aligned chunks, else per double with the tail guarded
+template <bool VEC>
+__device__ __forceinline__ double2 f64_load_chunk(const double *__restrict__ src, size_t row, int vd, int ch)
+{
+    const double *p = src + row * vd + 2 * ch;
+    if constexpr (VEC) return *reinterpret_cast<const double2 *>(p);
+    double2 x = VecOps<double2>::zero();
+    x.x = p[0];
+    if (vd - 2 * ch > 1) x.y = p[1];
+    return x;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void f64_store_chunk(double *__restrict__ out, size_t row, int vd, int ch, double2 a)
+{
+    double *o = out + row * vd + 2 * ch;
+    if constexpr (VEC) { *reinterpret_cast<double2 *>(o) = a; return; }
+    o[0] = a.x;
+    if (vd - 2 * ch > 1) o[1] = a.y;
+}
+
+// corners [j0, j1) of one vertex; csr_row carries the segment-head flag of the fp32 scan in its sign bit (a row-range
+// table's rows have it clear)
+template <bool VEC>
+__device__ __forceinline__ double2 f64_vertex_sum(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
+                                                  const double *__restrict__ src, int vd, int ch)
+{
+    double2 acc = VecOps<double2>::zero();
+    for (int j = j0; j < j1; ++j)
+        VecOps<double2>::fma(acc, (double)w[j], f64_load_chunk<VEC>(src, (size_t)(row[j] & 0x7FFFFFFF), vd, ch));
+    return acc;
+}
+
+// sum_r w_r values[v_r][ch] in corner order, then ONE division by 1 + 2^-d
+__device__ __forceinline__ double2 f64_point_sum(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
+                                                 int d1, const double2 *__restrict__ values, int nch, int ch, double denom)
+{
+    double2 acc = VecOps<double2>::zero();
+    for (int r = 0; r < d1; ++r)
+        VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)evid[(size_t)r * n + p] * nch + ch]);
+    return make_double2(acc.x / denom, acc.y / denom);
+}
+
+constexpr int kF64ChunkMax = 64;      // chunks one lane group can cover: a group never spans two waves
+static inline bool f64_vec_ok(const void *p, int vd) { return (vd & 1) == 0 && ((uintptr_t)p & 15) == 0; }
+static inline int f64_group_shift(int nch)
+{
+    int s = 0;
+    while ((1 << s) < nch) ++s;
+    return s;
+}
+
+// The gather slices of plx_rows.hip, plx_f64.hip and plx_rows_f64.hip have d + 1 compiled in up to kGatherMaxD1:
 // f(std::integral_constant<int, D1>) with D1 = d1 for 2..20, else 0 (the run-time form).
 constexpr int kGatherMaxD1 = 20;
 template <class F> static inline void dispatch_d1(int d1, F &&f)

@@ -141,7 +141,7 @@ static int compact_range(plx_lattice *L, const uint32_t *keys, uint32_t mask, in
 }
 
 // The slot of a range: the one that holds it, else an empty one, else the least recently used.
-static plx_lattice::RowsRange *range_slot(plx_lattice *L, int64_t begin, int64_t count)
+plx_lattice::RowsRange *range_slot(plx_lattice *L, int64_t begin, int64_t count)
 {
     plx_lattice::RowsRange *pick = nullptr;
     for (auto &r : L->rows) {
@@ -161,7 +161,7 @@ static plx_lattice::RowsRange *range_slot(plx_lattice *L, int64_t begin, int64_t
     return pick;
 }
 
-static int ensure_rows_splat(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream)
+int ensure_rows_splat(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream)
 {
     if (r->splat_ready) return PLX_OK;
     PLX_TRY(refuse_under_capture(stream, "the corner table of this row range"));
@@ -179,7 +179,7 @@ static int ensure_rows_splat(plx_lattice *L, plx_lattice::RowsRange *r, hipStrea
     return PLX_OK;
 }
 
-static int ensure_rows_slice(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream)
+int ensure_rows_slice(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream)
 {
     if (r->slice_ready) return PLX_OK;
     PLX_TRY(refuse_under_capture(stream, "the position table of this row range"));

@@ -29,7 +29,7 @@ def _taps_array(coeffs):
 
 
 def _check_f32_cuda(t, name, ndim=2, f64_ok=False):
-    """f64_ok: the call has a float64 form (the stages and the product, not the build or the rows calls)."""
+    """f64_ok: the call has a float64 form (the stages, the product and the rows calls, not the build)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not t.is_cuda:
@@ -416,57 +416,75 @@ class Lattice:
         return begin, count
 
     def splat_rows(self, src, row_begin, values=None):
-        """values = S^T restricted to the caller's rows [row_begin, row_begin + len(src)); every vertex row is written."""
-        _check_f32_cuda(src, "src")
+        """values = S^T restricted to the caller's rows [row_begin, row_begin + len(src)); every vertex row is written.  In the
+        dtype of `src` (float64: plx_splat_rows_f64, over the same range tables)."""
+        _check_f32_cuda(src, "src", f64_ok=True)
         src = src.contiguous()
         begin, count = self._rows(row_begin, src.shape[0])
         vd = src.shape[1]
+        f64 = src.dtype == torch.float64
         if values is None:
-            values = self.new_values(vd)
-        assert values.shape == (self.m, self.values_stride(vd)) and values.is_contiguous()
+            values = self.new_values(vd, src.dtype)
+        elif values.dtype != src.dtype:
+            raise TypeError(f"values must be {src.dtype} like src, got {values.dtype}")
+        assert values.shape == (self.m, self.values_stride(vd, src.dtype)) and values.is_contiguous()
+        fn, name = (nv.lib().plx_splat_rows_f64, "plx_splat_rows_f64") if f64 else (nv.lib().plx_splat_rows, "plx_splat_rows")
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_splat_rows(self._h, ctypes.c_void_p(src.data_ptr()), begin, count, vd,
-                                         ctypes.c_void_p(values.data_ptr()), _stream_ptr(self.device))
-        nv.check(rc, "plx_splat_rows")
+            rc = fn(self._h, ctypes.c_void_p(src.data_ptr()), begin, count, vd, ctypes.c_void_p(values.data_ptr()),
+                    _stream_ptr(self.device))
+        nv.check(rc, name)
         return values
 
     def slice_rows(self, values, row_begin, row_count, out=None, vd=None):
-        """out[row_count, vd] = rows [row_begin, row_begin + row_count) of S values / (1 + 2^-d)."""
-        _check_f32_cuda(values, "values")
+        """out[row_count, vd] = rows [row_begin, row_begin + row_count) of S values / (1 + 2^-d), in the dtype of `values`."""
+        _check_f32_cuda(values, "values", f64_ok=True)
         vd = values.shape[1] if vd is None else vd
-        assert values.shape[1] == self.values_stride(vd) and values.is_contiguous()
+        assert values.shape[1] == self.values_stride(vd, values.dtype) and values.is_contiguous()
         begin, count = self._rows(row_begin, row_count)
         if out is None:
-            out = torch.empty((count, vd), dtype=torch.float32, device=self.device)
+            out = torch.empty((count, vd), dtype=values.dtype, device=self.device)
+        elif out.dtype != values.dtype:
+            raise TypeError(f"out must be {values.dtype} like values, got {out.dtype}")
         assert out.shape == (count, vd) and out.is_contiguous()
+        f64 = values.dtype == torch.float64
+        fn, name = (nv.lib().plx_slice_rows_f64, "plx_slice_rows_f64") if f64 else (nv.lib().plx_slice_rows, "plx_slice_rows")
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_slice_rows(self._h, ctypes.c_void_p(values.data_ptr()), vd, begin, count,
-                                         ctypes.c_void_p(out.data_ptr()), _stream_ptr(self.device))
-        nv.check(rc, "plx_slice_rows")
+            rc = fn(self._h, ctypes.c_void_p(values.data_ptr()), vd, begin, count, ctypes.c_void_p(out.data_ptr()),
+                    _stream_ptr(self.device))
+        nv.check(rc, name)
         return out
 
     def apply_rows(self, src, src_begin, out_begin, out_count, out=None):
         """out[out_count, vd] = K[out rows, src rows] src: rows [out_begin, out_begin + out_count) of apply() of the
-        n-row matrix that holds `src` in rows [src_begin, src_begin + len(src)) and zeros elsewhere (plx_apply_rows).
+        n-row matrix that holds `src` in rows [src_begin, src_begin + len(src)) and zeros elsewhere (plx_apply_rows; float64:
+        plx_apply_rows_f64, equal as values to those rows of the float64 apply()).
         Rows are in the caller's order whatever set_lattice_row_order() says."""
-        _check_f32_cuda(src, "src")
+        _check_f32_cuda(src, "src", f64_ok=True)
         src = src.contiguous()
         sb, sc = self._rows(src_begin, src.shape[0])
         ob, oc = self._rows(out_begin, out_count)
         vd = src.shape[1]
         if out is None:
-            out = torch.empty((oc, vd), dtype=torch.float32, device=self.device)
+            out = torch.empty((oc, vd), dtype=src.dtype, device=self.device)
+        elif out.dtype != src.dtype:
+            raise TypeError(f"out must be {src.dtype} like src, got {out.dtype}")
         assert out.shape == (oc, vd) and out.is_contiguous()
+        f64 = src.dtype == torch.float64
+        fn, name = (nv.lib().plx_apply_rows_f64, "plx_apply_rows_f64") if f64 else (nv.lib().plx_apply_rows, "plx_apply_rows")
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_apply_rows(self._h, ctypes.c_void_p(src.data_ptr()), sb, sc, vd,
-                                         ctypes.c_void_p(out.data_ptr()), ob, oc, _stream_ptr(self.device))
-        nv.check(rc, "plx_apply_rows")
+            rc = fn(self._h, ctypes.c_void_p(src.data_ptr()), sb, sc, vd, ctypes.c_void_p(out.data_ptr()), ob, oc,
+                    _stream_ptr(self.device))
+        nv.check(rc, name)
         return out
 
     def rows_kernels(self):
-        """Kernels launched by the last splat_rows / slice_rows (or apply_rows) on this lattice: {"splat": [...],
+        """Kernels launched by the last float32 splat_rows / slice_rows (or apply_rows) on this lattice: {"splat": [...],
         "slice": [...]}; the blur of apply_rows reports through stage_kernels()."""
         return self._last_kernels("plx_last_rows_kernels", 256)
+
+    def rows_f64_kernels(self):
+        """... and by the last float64 ones; the blur of a float64 apply_rows reports through f64_kernels()."""
+        return self._last_kernels("plx_last_rows_f64_kernels", 256)
 
     def accepts_rows(self):
         """True when the rows calls serve this lattice: a plain single-shard build without the "reference_growth" replay."""

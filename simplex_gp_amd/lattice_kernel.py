@@ -324,12 +324,14 @@ class LatticeRowsProduct(Function):
         return grad_source, None, None, None, None, None, None
 
 
-def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1):
-    """Whether K(xin, xout) @ V goes through the native row-range product: a CUDA fp32 2-D right-hand side, no test hook /
-    foreign filter installed (LatticeFilterGeneral.method), no gradient wanted for the positions, the route switched
-    on (RectangularLazyLattice.native_rows) and, where the caller says how many columns V has, at least `min_columns`
-    of them (RectangularLazyLattice.native_min_columns).  Everything else takes the padded square filter."""
-    return bool(enabled and device_type == "cuda" and dtype == torch.float32 and dim == 2 and hook is None
+def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1, f64=False):
+    """Whether K(xin, xout) @ V goes through the native row-range product: a CUDA fp32 2-D right-hand side -- or, with
+    f64=True (RectangularLazyLattice.native_rows_f64), a float64 one --, no test hook / foreign filter installed
+    (LatticeFilterGeneral.method), no gradient wanted for the positions, the route switched on
+    (RectangularLazyLattice.native_rows) and, where the caller says how many columns V has, at least `min_columns` of them
+    (RectangularLazyLattice.native_min_columns).  Everything else takes the padded square filter."""
+    dtype_ok = dtype == torch.float32 or (bool(f64) and dtype == torch.float64)
+    return bool(enabled and device_type == "cuda" and dtype_ok and dim == 2 and hook is None
                 and not requires_grad and (columns is None or columns >= min_columns))
 
 
@@ -374,10 +376,16 @@ class RectangularLazyLattice(LazyTensor):
     (profiles/rows_measured.md): at 101 columns (a prediction split) the native product is 10 % faster than the padded one
     and needs 1.25 GB less; at 11 and at 1 column its vertex-gather splat loses to the square stages' tuned narrow kernels
     (0.89 against 0.68 ms, 0.59 against 0.24 ms).  The crossover between 11 and 101 has not been located, so everything
-    below the measured winning width keeps the padded path."""
+    below the measured winning width keeps the padded path.
+
+    native_rows_f64: whether a float64 V takes the native route too (plx_apply_rows_f64; the same width gate).  The
+    native and the padded float64 products are equal as values, so the switch changes time and
+    memory only.  It is off until the native product has been measured no slower than the padded one at 101 columns in
+    both directions (profiles/rows_f64_measured.md: not measured yet)."""
 
     native_rows = True
     native_min_columns = 101
+    native_rows_f64 = False
 
     def __init__(self, xin, xout, dkernel=None):
         super().__init__(xin, xout, dkernel=dkernel)
@@ -391,7 +399,7 @@ class RectangularLazyLattice(LazyTensor):
         assert V.shape[-2] == n_out, f"mismatched shapes? {V.shape, self.xout.shape}"
         wants_grad = torch.is_grad_enabled() and (self.xin.requires_grad or self.xout.requires_grad)
         if rows_route(V.device.type, V.dtype, V.dim(), LatticeFilterGeneral.method, wants_grad, type(self).native_rows,
-                      V.shape[-1], type(self).native_min_columns):
+                      V.shape[-1], type(self).native_min_columns, f64=type(self).native_rows_f64):
             base, swapped = self.__dict__.get("_rows_base", (self, False))
             stacked = base._stacked_points()                       # [base.xout; base.xin]: one lattice for both directions
             coeffs = self.dkernel.get_coeffs()
