@@ -332,6 +332,52 @@ int plx_apply_rows_f64(plx_lattice *lat, const double *d_src, int64_t src_begin,
 int plx_last_rows_f64_kernels(const plx_lattice *lat, char *buf, int cap);   /* "splat=...;slice=..." */
 
 /*
+ * The float64 conjugate-gradient solve on the float64 product (callers detect it by symbol; the version string is
+ * unchanged): the vector work of a batched CG iteration and the (s K + sigma^2 I) v of a GP solve, in double.
+ *   plx_coldot_f64             d_out[c] = sum_r a[r][c] b[r][c]; d_work: plx_coldot_work_doubles(vd) doubles (-1 for a vd
+ *                              outside 1..256; monotone inside).
+ *   plx_cg_step_update_f64     alpha = active ? rs / max(pAp, 1e-300) : 0;  X += alpha P;  R -= alpha AP;  rs_new = |R|^2
+ *                              (d_work as for plx_coldot_f64).
+ *   plx_cg_step_direction_f64  beta = active ? rs_new / max(rs, 1e-300) : 0;  P = R + beta P;
+ *                              active_out = active and sqrt(rs_new) / b_norm > tol     (active_out != active).
+ * These are plx_coldot / plx_cg_step_update / plx_cg_step_direction with EVERY array in double (row-major [n][vd] matrices;
+ * alpha, beta, rs, pAp, b_norm and active -- 1.0 / 0.0 -- double [vd]).  The guard is 1e-300 instead of the fp32 calls'
+ * 1e-30: a double solve of a right-hand side scaled by 1e-20 has pAp near 1e-40, which the fp32 guard would silently turn
+ * into a wrong alpha.  1 <= vd <= 256, n >= 1.  Deterministic: partial sums per workgroup, then a fixed-order final sum; no
+ * float atomics; two calls with the same arguments are bit-equal.  They never allocate and never synchronise, so they
+ * are graph-capturable.  Every argument is checked before any launch: a NULL pointer, a vd outside the range, n < 1, a
+ * pointer that is not 8-byte aligned and d_active_out == d_active are PLX_ERR_INVALID.
+ *   plx_apply_affine_f64       d_out = a * (K d_src) + b * d_src with (a, b) = d_scale_shift[0..1], two doubles read on the
+ *                              device.  K d_src is the value plx_apply_f64 gives (its splat and blur run unchanged on the
+ *                              same workspace; the slice has the tail fused); out = fma(a, y, b * x) per element.  Rows in the
+ *                              caller's order, as for every fp64 call.  Scope, refusals, workspace and the capture rule are
+ *                              those of plx_apply_f64; in addition d_out must not alias d_src (PLX_ERR_INVALID).
+ *                              d_dot (optional): d_dot[c] = <d_src[:, c], d_out[:, c]> for c < vd, from the slice kernel's
+ *                              registers -- one partial row per workgroup in d_work, in a fixed order, then the final
+ *                              stage of plx_coldot_f64.  Served for vd <= 128 (rows of up to 64 chunks); d_dot != NULL with
+ *                              vd > 128 is PLX_ERR_INVALID: pass NULL and call plx_coldot_f64.
+ *   plx_affine_dot_work_doubles  doubles of d_work for that d_dot; -1 where the dot is not served or the lattice is not
+ *                              built.  With d_dot == NULL, d_work may be NULL.
+ * The slice reports through plx_last_f64_kernels, in the slice field (f64_affine_v1_kernel / f64_affine_chunk_kernel /
+ * f64_affine_wide_kernel, gated like the slices of plx_apply_f64).
+ * Two exactness contracts: (i) with (a, b) = (1, 0) d_out equals plx_apply_f64 AS VALUES (-0.0 counted equal to +0.0; finite
+ * d_src): the sums are formed from the same pieces in the same order and the tail adds 0.  (ii) d_dot and
+ * plx_coldot_f64(d_src, d_out) agree to (n + 4) 2^-52 of sum_r |src out| each, not to the bit: their partial sums are cut
+ * differently (by workgroups of lattice-ordered points there, by ranges of caller rows here).
+ */
+int64_t plx_coldot_work_doubles(int vd);
+int plx_coldot_f64(const double *d_a, const double *d_b, int64_t n, int vd, double *d_out, double *d_work, void *stream);
+int plx_cg_step_update_f64(double *d_x, double *d_r, const double *d_p, const double *d_ap, const double *d_rs,
+                           const double *d_pap, const double *d_active, int64_t n, int vd, double *d_rs_new,
+                           double *d_alpha, double *d_work, void *stream);
+int plx_cg_step_direction_f64(double *d_p, const double *d_r, const double *d_rs_new, const double *d_rs,
+                              const double *d_active, const double *d_b_norm, double tol, int64_t n, int vd,
+                              double *d_beta, double *d_active_out, void *stream);
+int64_t plx_affine_dot_work_doubles(const plx_lattice *lat, int vd);
+int plx_apply_affine_f64(plx_lattice *lat, const double *d_src, int vd, double *d_out, const double *d_scale_shift,
+                         double *d_dot, double *d_work, void *stream);
+
+/*
  * The reference's one-shot call (cpp:6-10 -> h:259-340): build a lattice for
  * d_ref, apply it to d_src, leave nothing behind.  `scratch` may be NULL or a
  * lattice object whose buffers are reused (avoids hipMalloc in steady state; it

@@ -71,6 +71,12 @@ _SIGNATURES = {
     "plx_slice_rows_f64": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _vp]),
     "plx_apply_rows_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
     "plx_last_rows_f64_kernels": (_i32, [_vp, ctypes.c_char_p, _i32]),
+    "plx_coldot_work_doubles": (_i64, [_i32]),
+    "plx_coldot_f64": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "plx_cg_step_update_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "plx_cg_step_direction_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i64, _i32, _vp, _vp, _vp]),
+    "plx_affine_dot_work_doubles": (_i64, [_vp, _i32]),
+    "plx_apply_affine_f64": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "plx_filter": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _f32p, _i32, _vp, _vp]),
     "plx_coldot": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "plx_coldot_work_floats": (_i64, [_i32]),

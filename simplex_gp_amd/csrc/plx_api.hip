@@ -630,6 +630,42 @@ int plx_apply_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, vo
     return slice_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, d_out, s);
 }
 
+// ---- the float64 affine product of a CG iteration (slice + tail + dot: plx_cg_f64.hip) --------------------------------------
+int64_t plx_affine_dot_work_doubles(const plx_lattice *L, int vd)
+{
+    if (!L || !L->built || vd < 1) return -1;
+    const int rows = affine_f64_dot_rows(L, vd);
+    return rows > 0 ? (int64_t)rows * values_stride_f64(vd) : -1;
+}
+
+int plx_apply_affine_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, const double *d_scale_shift, double *d_dot,
+                         double *d_work, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_src, d_out, vd, "plx_apply_affine_f64"));
+    if (!d_scale_shift) { set_error("plx_apply_affine_f64: NULL scale/shift"); return PLX_ERR_INVALID; }
+    if (d_dot && !d_work) { set_error("plx_apply_affine_f64: d_dot needs d_work (plx_affine_dot_work_doubles)"); return PLX_ERR_INVALID; }
+    PLX_TRY(check_doubles_aligned(d_scale_shift, d_dot, "plx_apply_affine_f64"));
+    PLX_TRY(check_doubles_aligned(d_work, nullptr, "plx_apply_affine_f64"));
+    if (d_src == d_out) { set_error("plx_apply_affine_f64: d_out must not alias d_src"); return PLX_ERR_INVALID; }
+    const int dot_rows = d_dot ? affine_f64_dot_rows(L, vd) : 0;
+    if (d_dot && dot_rows < 1) {
+        set_error("plx_apply_affine_f64: the fused dot serves vd <= 128, got %d (pass d_dot = NULL and use plx_coldot_f64)", vd);
+        return PLX_ERR_INVALID;
+    }
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    PLX_TRY(ensure(L->val64_a, (size_t)L->m * values_stride_f64(vd) * 8));      // the workspace of plx_apply_f64
+    PLX_TRY(ensure(L->val64_b, (size_t)L->m * values_stride_f64(vd) * 8));
+    PLX_TRY(splat_f64_impl(L, d_src, vd, L->val64_a.as<double>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), vd, &in_b, s));
+    PLX_TRY(slice_affine_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, d_src, d_scale_shift, d_out,
+                                  d_dot ? d_work : nullptr, s));
+    if (!d_dot) return PLX_OK;
+    return coldot_final_f64(d_work, dot_rows, values_stride_f64(vd), vd, d_dot, s);
+}
+
 int plx_last_f64_kernels(const plx_lattice *L, char *buf, int cap)
 {
     if (!L || !buf || cap < 1) return PLX_ERR_INVALID;

@@ -385,6 +385,13 @@ int slice_rows_f64_impl(plx_lattice *L, const double *d_values, int vd, int64_t 
 int splat_f64_impl(plx_lattice *L, const double *d_src, int vd, double *d_values, hipStream_t stream);
 int blur_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
 int slice_f64_impl(plx_lattice *L, const double *d_values, int vd, double *d_out, hipStream_t stream);
+// plx_cg_f64.hip: the fp64 slice with the affine tail out = a y + b src fused (and, unless d_partial is NULL, one partial
+// row of <src, out> per workgroup: affine_f64_dot_rows rows of values_stride_f64(vd) doubles; 0 rows: the shape serves no
+// dot), and the final stage of plx_coldot_f64: out[c] = sum over nrows of partial[k * stride + c], c < vd, fixed order
+int affine_f64_dot_rows(const plx_lattice *L, int vd);
+int slice_affine_f64_impl(plx_lattice *L, const double *d_values, int vd, const double *d_src, const double *d_ss,
+                          double *d_out, double *d_partial, hipStream_t stream);
+int coldot_final_f64(const double *d_partial, int nrows, int stride, int vd, double *d_out, hipStream_t stream);
 // plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
 int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,

@@ -68,6 +68,7 @@ class Lattice:
         self._own_begin = 0
         self.lattice_rows = False
         self._dot_work = None
+        self._dot_work64 = None   # float64 partial sums of apply_affine(want_dot=True) in double: grow-only, separate
         self.build_id = 0         # counts the builds of this object (holders of per-build data compare it)
         self._merged = False      # built by build_local + build_merge (one rank's rows of a sharded lattice)
 
@@ -493,11 +494,17 @@ class Lattice:
         return not self.reference_growth_info()["replayed"]
 
     def apply_affine(self, src, scale_shift, out=None, want_dot=False):
-        """out = a * K src + b * src with (a, b) = scale_shift (a 2-element float32 tensor on the device, read
-        there: no host synchronisation on hyper-parameters).  want_dot: also return the column-wise <src, out>
+        """out = a * K src + b * src with (a, b) = scale_shift (a 2-element tensor on the device, of the dtype of `src`, read
+        there: no host synchronisation on hyper-parameters).  float64: plx_apply_affine_f64, rows always in the caller's
+        order, want_dot=True for up to 128 columns, no want_dot="partial"; a mixed pair is a TypeError.  want_dot: also return the column-wise <src, out>
         (the p^T A p of a CG iteration), formed inside the slice kernel; needs 2..256 columns.  want_dot="partial":
         return (out, work, tiles) with the per-tile partial sums of those dots left un-reduced in `work` (the fused CG
         step adds them up itself); `work` is the lattice's own buffer, valid until the next such call."""
+        if isinstance(src, torch.Tensor) and isinstance(scale_shift, torch.Tensor) and src.dtype != scale_shift.dtype:
+            raise TypeError(f"src and scale_shift must both be float32 or both float64, got {src.dtype} and "
+                            f"{scale_shift.dtype}")
+        if isinstance(src, torch.Tensor) and src.dtype == torch.float64:
+            return self._apply_affine_f64(src, scale_shift, out, want_dot)
         src = self._src(src, self.n_owned)
         _check_f32_cuda(scale_shift, "scale_shift", ndim=1)
         assert scale_shift.numel() == 2 and scale_shift.is_contiguous()
@@ -532,6 +539,42 @@ class Lattice:
                                            ctypes.c_void_p(scale_shift.data_ptr()), _stream_ptr(self.device))
         nv.check(rc, "plx_apply_affine")
         return out
+
+    def affine_dot_f64_ok(self, vd):
+        """True when the float64 apply_affine(want_dot=True) serves vd columns on this build (plx_affine_dot_work_doubles)."""
+        return int(nv.lib().plx_affine_dot_work_doubles(self._h, int(vd))) >= 0
+
+    def _apply_affine_f64(self, src, scale_shift, out, want_dot):
+        """The float64 form of apply_affine (plx_apply_affine_f64): rows in the caller's order, scale_shift a float64
+        2-vector on the device; want_dot=True for up to 128 columns; there is no fused CG step in double, hence no
+        want_dot="partial"."""
+        if want_dot == "partial":
+            raise ValueError('apply_affine(want_dot="partial") has no float64 form: there is no fused CG step in double')
+        src = self._src(src, self.n_owned, f64_ok=True)
+        _check_f32_cuda(scale_shift, "scale_shift", ndim=1, f64_ok=True)
+        assert scale_shift.numel() == 2 and scale_shift.is_contiguous()
+        vd = src.shape[1]
+        if out is None:
+            out = torch.empty((self.n_owned, vd), dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64:
+            raise TypeError(f"out must be torch.float64 like src, got {out.dtype}")
+        L = nv.lib()
+        dot = work = None
+        if want_dot:
+            need = int(L.plx_affine_dot_work_doubles(self._h, vd))
+            if need < 0:
+                raise ValueError(f"apply_affine(want_dot=True) in float64 needs 1..128 columns on a built lattice, got {vd}")
+            if self._dot_work64 is None or self._dot_work64.numel() < need:
+                self._dot_work64 = torch.empty(need, dtype=torch.float64, device=self.device)
+            work = self._dot_work64
+            dot = torch.empty(vd, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = L.plx_apply_affine_f64(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                                        ctypes.c_void_p(scale_shift.data_ptr()),
+                                        ctypes.c_void_p(dot.data_ptr()) if want_dot else None,
+                                        ctypes.c_void_p(work.data_ptr()) if want_dot else None, _stream_ptr(self.device))
+        nv.check(rc, "plx_apply_affine_f64")
+        return (out, dot) if want_dot else out
 
     @staticmethod
     def backward_fusable(nrhs, d):

@@ -31,32 +31,55 @@ def _colsum(a, b, reduce=None):
     """Column-wise <a, b> of two [n, t] matrices (summed over ranks through `reduce`).
     On the GPU this is libplx's plx_coldot (torch's (a*b).sum(0) is ~60x slower on
     tall, narrow row-major matrices); elsewhere plain torch."""
-    if (a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 2
+    if (a.is_cuda and a.dtype == b.dtype and (a.dtype == torch.float32 or _f64_native(a)) and a.dim() == 2
             and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape and a.shape[1] <= 256):
         import ctypes
         from . import _native as nv
         n, t = a.shape
-        key = (a.device.index, t)
-        work = _dot_work.get(key)
-        if work is None:
-            work = _dot_work[key] = torch.empty(int(nv.lib().plx_coldot_work_floats(t)), dtype=torch.float32,
-                                                device=a.device)
-        out = torch.empty(t, dtype=torch.float32, device=a.device)
+        f64 = a.dtype == torch.float64
+        work = _coldot_work(a.device, t, a.dtype)
+        out = torch.empty(t, dtype=a.dtype, device=a.device)
+        fn, name = (nv.lib().plx_coldot_f64, "plx_coldot_f64") if f64 else (nv.lib().plx_coldot, "plx_coldot")
         with torch.cuda.device(a.device):
-            rc = nv.lib().plx_coldot(ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), n, t,
-                                     ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(work.data_ptr()),
-                                     ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-        nv.check(rc, "plx_coldot")
+            rc = fn(ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), n, t,
+                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+                    ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
+        nv.check(rc, name)
         s = out
     else:
         s = (a * b).sum(0)
     return reduce(s) if reduce is not None else s
 
 
-def _native_ok(*ts):
+# The float64 solve on the native double kernels (plx_coldot_f64, plx_cg_step_update_f64, plx_cg_step_direction_f64): True
+# by default; False sends float64 back to the torch loop (the A/B of tools/cg_f64_time.py; profiles/cg_f64_measured.md).
+NATIVE_CG_F64 = True
+
+
+def _f64_native(t):
+    """A float64 tensor the native double kernels take: the switch is on and the tensor is not empty (they serve n >= 1)."""
+    return t.dtype == torch.float64 and NATIVE_CG_F64 and t.numel() > 0
+
+
+def _coldot_work(device, t, dtype):
+    """The partial-sum buffer of the column reductions for t columns, per device and dtype (grow-never: its size depends on
+    t alone)."""
+    from . import _native as nv
+    f64 = dtype == torch.float64
+    key = (device.index, t, "f64") if f64 else (device.index, t)
+    work = _dot_work.get(key)
+    if work is None:
+        size = nv.lib().plx_coldot_work_doubles(t) if f64 else nv.lib().plx_coldot_work_floats(t)
+        work = _dot_work[key] = torch.empty(int(size), dtype=dtype, device=device)
+    return work
+
+
+def _native_ok(*ts, f64_ok=False):
+    """All tensors contiguous 2-D CUDA matrices of one shape, at most 256 columns, all float32 -- or, with f64_ok (the
+    calls that have a double form), all float64 while NATIVE_CG_F64 is on."""
     t0 = ts[0]
-    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape == t0.shape
-               for t in ts) and t0.shape[1] <= 256
+    return all(t.is_cuda and (t.dtype == torch.float32 or (f64_ok and _f64_native(t))) and t.dtype == t0.dtype and t.dim() == 2
+               and t.is_contiguous() and t.shape == t0.shape for t in ts) and t0.shape[1] <= 256
 
 
 def _cg_update(X, R, P, AP, alpha, reduce=None):
@@ -603,7 +626,7 @@ def batched_cg(matmul, B, max_iter=1000, tol=1e-4, reduce=None, want_tridiag=Fal
         return _batched_pcg_native(matmul, B, precond, max_iter, tol, want_tridiag, check_every, matmul_dot, floor)
     if precond is not None:
         return _batched_pcg(matmul, B, precond, max_iter, tol, reduce, want_tridiag, check_every, floor)
-    if reduce is None and _native_ok(B):
+    if reduce is None and _native_ok(B, f64_ok=True):
         return _batched_cg_native(matmul, B, max_iter, tol, want_tridiag, check_every, matmul_dot, floor)
     X = torch.zeros_like(B)
     R = B.clone().contiguous()
@@ -661,22 +684,26 @@ def _batched_cg_native(matmul, B, max_iter, tol, want_tridiag, check_every, matm
     R = B.clone().contiguous()
     P = R.clone()
     rs = _colsum(R, R)
-    b_norm = rs.sqrt().clamp_min(1e-30)
-    active = torch.ones(t, dtype=torch.float32, device=dev)
+    b_norm = rs.sqrt().clamp_min(1e-300 if B.dtype == torch.float64 else 1e-30)
+    # every small array in the dtype of B: the double iteration is the same loop on plx_cg_step_update_f64 /
+    # plx_cg_step_direction_f64 (no fused step forms in double)
+    f64 = B.dtype == torch.float64
+    step_update, step_update_name = (lib.plx_cg_step_update_f64, "plx_cg_step_update_f64") if f64 \
+        else (lib.plx_cg_step_update, "plx_cg_step_update")
+    step_direction, step_direction_name = (lib.plx_cg_step_direction_f64, "plx_cg_step_direction_f64") if f64 \
+        else (lib.plx_cg_step_direction, "plx_cg_step_direction")
+    active = torch.ones(t, dtype=B.dtype, device=dev)
     active_next = torch.empty_like(active)
     rs_new = torch.empty_like(rs)
-    key = (dev.index, t)
-    work = _dot_work.get(key)
-    if work is None:
-        work = _dot_work[key] = torch.empty(int(lib.plx_coldot_work_floats(t)), dtype=torch.float32, device=dev)
+    work = _coldot_work(dev, t, B.dtype)
     kmax = max_iter
-    alphas = torch.zeros(kmax if want_tridiag else 1, t, dtype=torch.float32, device=dev)
-    betas = torch.zeros(kmax if want_tridiag else 1, t, dtype=torch.float32, device=dev)
+    alphas = torch.zeros(kmax if want_tridiag else 1, t, dtype=B.dtype, device=dev)
+    betas = torch.zeros(kmax if want_tridiag else 1, t, dtype=B.dtype, device=dev)
     p = lambda a: ctypes.c_void_p(a.data_ptr())          # noqa: E731
     it = 0
     # the iteration without its two stand-alone reductions (plx_cg_step_*_fused): rows of whole 16-byte chunks, and an
     # MVM that can leave its <P, AP> partial sums un-reduced (matmul_dot.partial)
-    partial_mm = getattr(matmul_dot, "partial", None) if _fuse_cg_steps(n) else None
+    partial_mm = getattr(matmul_dot, "partial", None) if _fuse_cg_steps(n) and not f64 else None
     fused = partial_mm is not None and int(lib.plx_cg_fused_work_floats(t)) > 0
     if fused:
         fkey = (dev.index, t, "fused")
@@ -708,11 +735,11 @@ def _batched_cg_native(matmul, B, max_iter, tol, want_tridiag, check_every, matm
                 AP = AP if AP.is_contiguous() else AP.contiguous()
                 pAp = _colsum(P, AP)
             row = it - 1 if want_tridiag else 0
-            nv.check(lib.plx_cg_step_update(p(X), p(R), p(P), p(AP), p(rs), p(pAp), p(active), n, t, p(rs_new),
-                                            p(alphas[row]), p(work), stream), "plx_cg_step_update")
+            nv.check(step_update(p(X), p(R), p(P), p(AP), p(rs), p(pAp), p(active), n, t, p(rs_new),
+                                 p(alphas[row]), p(work), stream), step_update_name)
             step_tol = float(tol) if it >= floor else min(float(tol), _FROZEN_BELOW)
-            nv.check(lib.plx_cg_step_direction(p(P), p(R), p(rs_new), p(rs), p(active), p(b_norm), step_tol, n, t,
-                                               p(betas[row]), p(active_next), stream), "plx_cg_step_direction")
+            nv.check(step_direction(p(P), p(R), p(rs_new), p(rs), p(active), p(b_norm), step_tol, n, t,
+                                    p(betas[row]), p(active_next), stream), step_direction_name)
             rs, rs_new = rs_new, rs
             active, active_next = active_next, active
             if tol > 0 and (it % check_every == 0 or it == max_iter) and not bool(active.any()):
@@ -876,6 +903,11 @@ class LatticeGP(nn.Module):
                 else lk.position_hint(x.div(self.kernel.lengthscale), x, scale_of=getattr(self.kernel, "raw_lengthscale", None))
             ref = ref if ref.is_contiguous() else lk.carry_hint(ref.contiguous(), ref)
             lat = lk.lattice_cache().get(ref, self.kernel.dkernel_fn.get_coeffs())
+            if x.dtype == torch.float64:
+                # the float64 product keeps the caller's row order: the affine closure in double, identity permutations
+                ss = torch.stack([self.outputscale.detach().reshape(()), self.noise.detach().reshape(())]).to(torch.float64).contiguous()
+                yield (lambda V: lat.apply_affine(V.contiguous(), ss)), (lambda v: v), (lambda v: v)
+                return
             ss = torch.stack([self.outputscale.detach().reshape(()), self.noise.detach().reshape(())]).to(torch.float32).contiguous()
             lat.set_lattice_row_order(True)
             try:
@@ -940,7 +972,8 @@ class LatticeGP(nn.Module):
         """(s K + sigma^2 I)^-1 rhs by batched CG, no gradients.  On the HIP path the
         iteration runs in lattice row order: the right-hand side is permuted once, every
         MVM skips its two row permutations, the solution is permuted back once (dot
-        products do not care about row order)."""
+        products do not care about row order).  A float64 rhs runs the float64 product
+        and the native double iteration, rows in the caller's order throughout."""
         from . import lattice_kernel as lk
         with torch.no_grad():
             if lk.LatticeFilterGeneral.method is not None or not x.is_cuda:
@@ -963,6 +996,8 @@ class LatticeGP(nn.Module):
                 ref = pre.ref
             lat = lk.lattice_cache().get(ref, self.kernel.dkernel_fn.get_coeffs())
             s, noise = self.outputscale, self.noise
+            if rhs.dtype == torch.float64:
+                return self._khat_solve_f64(lat, rhs, s, noise, cg_args)
             lat.set_lattice_row_order(True)
             try:
                 native_pre = isinstance(pre, LatticePreconditioner) and pre.lat is lat and pre.build_id == lat.build_id
@@ -998,6 +1033,23 @@ class LatticeGP(nn.Module):
             finally:
                 lat.set_lattice_row_order(False)
             return lat.from_lattice_order(sol), info
+
+    @staticmethod
+    def _khat_solve_f64(lat, rhs, s, noise, cg_args):
+        """khat_solve for a float64 right-hand side: the float64 product takes and returns rows in the caller's order, so
+        nothing is permuted and the lattice's row order is never touched; no column padding either (fp64 rows need 8-byte
+        alignment only, and 16-byte accesses follow from an even column count).  Every MVM is plx_apply_affine_f64, with
+        <P, AP> out of its slice kernel where the width allows."""
+        if cg_args.get("precond") is not None:
+            # the caller-order branch of the fp32 solve: its factor's rows are in the caller's order too
+            return batched_cg(lambda V: lat.apply(V).mul_(s).addcmul_(V, noise), rhs, **cg_args)
+        ss = torch.stack([s.detach().reshape(()), noise.detach().reshape(())]).to(torch.float64).contiguous()
+        rhs = rhs.contiguous()
+        fused_dot = None
+        if lat.affine_dot_f64_ok(rhs.shape[1]):
+            def fused_dot(V):
+                return lat.apply_affine(V, ss, want_dot=True)
+        return batched_cg(lambda V: lat.apply_affine(V.contiguous(), ss), rhs, matmul_dot=fused_dot, **cg_args)
 
     def preconditioner(self, x, rank, K=None, factor_dtype=torch.float16):
         """Rank-`rank` pivoted-Cholesky preconditioner of (s K + sigma^2 I) (no gradients).  On the HIP path it is
