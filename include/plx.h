@@ -378,6 +378,54 @@ int plx_apply_affine_f64(plx_lattice *lat, const double *d_src, int vd, double *
                          double *d_dot, double *d_work, void *stream);
 
 /*
+ * The float64 position gradient (callers detect it by symbol; the version string is unchanged): plx_apply_backward with
+ * every array in double, for every column count.  `lat` is built with the DERIVATIVE taps on the positions rounded to
+ * float, as for every fp64 call; d_x [n][d] is the caller's FLOAT64 position matrix (not the rounded copy), d_g (the
+ * incoming gradient) and d_src (the forward right-hand side) are [n][nrhs], all rows in the caller's order.  With
+ * L = nrhs and C = 2 L (1 + d) (always even: a value row is L (1 + d) chunks of two doubles), the stacked matrix is
+ * [ g | g (x) x | src | src (x) x ], [n][C], the product blocks l-major (column L + l d + k holds g_l x_k).  Neither it
+ * nor its filtered image is stored by plx_apply_backward_f64.
+ *   plx_backward_splat_f64     d_values[m][C] = the plx_splat_f64 of the stacked matrix, each stack element formed inside
+ *                              the splat as ONE rounded double multiply (plain columns are copied) and accumulated as
+ *                              fma((double)w, element, acc) in the corner order of plx_splat_f64.  d_values is 16-byte
+ *                              aligned.
+ *   plx_backward_contract_f64  slice and contraction in one kernel: from d_values (blurred by plx_blur_f64 at vd = C) every
+ *                              point's filtered row [ wg | wgx | ws | wsx ] is formed on chip with the sums of
+ *                              plx_slice_f64 (one division by 1 + 2^-d) and contracted to
+ *                                d_grad_x[row][k] = -2 sum_l ( s_l x_k wg_l - s_l wgx_lk + g_l x_k ws_l - g_l wsx_lk ),  k < d,
+ *                              the sum started at 0 and taken for l ascending, the four terms in the order written, the
+ *                              products s_l x_k and g_l x_k formed first; unless d_grad_src is NULL,
+ *                              d_grad_src[row][l] = wg_l.
+ *   plx_apply_backward_f64     the two around the blur of plx_apply_f64, on the float64 workspace that plx_apply_f64 owns;
+ *                              the arguments of plx_apply_backward, in double.
+ * The kernels report through plx_last_f64_kernels: f64_backward_splat_chunk_kernel / f64_backward_splat_wide_kernel in the
+ * splat field, f64_backward_contract_chunk_kernel / f64_backward_contract_wide_kernel in the slice field (the chunk shape
+ * up to 64 chunks, i.e. C <= 128; the wide shape above).
+ * Column limit: the contraction keeps a point's row on chip, four rows of C doubles in the 64 KiB of LDS of a workgroup,
+ * so C <= 2048; above that every call returns PLX_ERR_INVALID before any launch.
+ * Scope, refusals, workspace growth and the capture rule are those of plx_apply_f64.  PLX_ERR_STATE: a lattice that is not
+ * built, a sharded or merged build, a build that replayed "reference_growth", the first call of a width (or the first fp64
+ * splat after a build) under stream capture.  PLX_ERR_INVALID: a NULL pointer other than d_grad_src, nrhs < 1, a pointer
+ * off 8-byte alignment, d_values off 16-byte alignment, an output that is an input or the other output.
+ * PLX_ERR_TOO_LARGE: m * C or n * C at or over 2^31.  Every argument is checked before any GPU work; from the second call
+ * of a width on, a call neither allocates nor synchronises (plx_device_bytes does not move) and is graph-capturable.
+ * No float atomics, every output element written by exactly one thread: two calls with the same arguments are bit-equal.
+ * Two contracts.  (i) Bits: plx_backward_splat_f64 equals AS VALUES (-0.0 counted equal to +0.0) plx_splat_f64 of the
+ * explicit stacked matrix formed in double with one multiply per product element; d_grad_src equals AS VALUES columns
+ * [0, L) of plx_apply_f64 of that matrix; the staged calls (splat, plx_blur_f64, contract) give the bits of
+ * plx_apply_backward_f64.  (ii) Bar: every entry of d_grad_x is within 2 (k + 4 (L + 1)) 2^-52 of the size of the terms it
+ * sums (k: the depth of the fp64 product's sums, tests/test_backward_f64_gpu.py) of the gradient formed from a float64
+ * filter of the stack; bit equality with a contraction written in torch is not promised (its sum runs in another order).
+ */
+int plx_backward_splat_f64(plx_lattice *lat, const double *d_g, const double *d_src, const double *d_x, int nrhs,
+                           double *d_values, void *stream);
+int plx_backward_contract_f64(plx_lattice *lat, const double *d_values, const double *d_g, const double *d_src,
+                              const double *d_x, int nrhs, double *d_grad_x, double *d_grad_src /* may be NULL */,
+                              void *stream);
+int plx_apply_backward_f64(plx_lattice *lat, const double *d_g, const double *d_src, const double *d_x, int nrhs,
+                           double *d_grad_x, double *d_grad_src /* may be NULL */, void *stream);
+
+/*
  * The reference's one-shot call (cpp:6-10 -> h:259-340): build a lattice for
  * d_ref, apply it to d_src, leave nothing behind.  `scratch` may be NULL or a
  * lattice object whose buffers are reused (avoids hipMalloc in steady state; it

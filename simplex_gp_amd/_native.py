@@ -77,6 +77,9 @@ _SIGNATURES = {
     "plx_cg_step_direction_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i64, _i32, _vp, _vp, _vp]),
     "plx_affine_dot_work_doubles": (_i64, [_vp, _i32]),
     "plx_apply_affine_f64": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plx_backward_splat_f64": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "plx_backward_contract_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "plx_apply_backward_f64": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "plx_filter": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _f32p, _i32, _vp, _vp]),
     "plx_coldot": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "plx_coldot_work_floats": (_i64, [_i32]),

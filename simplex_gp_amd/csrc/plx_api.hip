@@ -729,6 +729,78 @@ int plx_last_rows_f64_kernels(const plx_lattice *L, char *buf, int cap)
     return PLX_OK;
 }
 
+// ---- the float64 position gradient (kernels: plx_backward_f64.hip; blur: plx_f64.hip) ------------------------------------
+
+// Everything a float64 position-gradient call checks before any GPU work.  in[0..n_in): the input buffers; out[0..n_out): the
+// output buffers, of which only a trailing d_grad_src may be NULL.  What needs no lattice comes first; then check_f64 on
+// the 2 nrhs (1 + d) columns of the stack, which are whole 16-byte rows (the count is even).
+static int check_backward_f64(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
+                              bool last_out_optional, int nrhs, const char *who)
+{
+    if (!L) { set_error("%s: NULL lattice", who); return PLX_ERR_INVALID; }
+    for (int i = 0; i < n_in; ++i)
+        if (!in[i]) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    for (int o = 0; o < n_out; ++o)
+        if (!out[o] && !(last_out_optional && o == n_out - 1)) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (nrhs < 1) { set_error("%s: nrhs = %d must be positive", who, nrhs); return PLX_ERR_INVALID; }
+    for (int i = 0; i < n_in; ++i) PLX_TRY(check_doubles_aligned(in[i], nullptr, who));
+    for (int o = 0; o < n_out; ++o) PLX_TRY(check_doubles_aligned(out[o], nullptr, who));
+    for (int o = 0; o < n_out; ++o) {
+        if (!out[o]) continue;
+        bool alias = false;
+        for (int i = 0; i < n_in; ++i) alias |= out[o] == in[i];
+        for (int q = 0; q < o; ++q) alias |= out[o] == out[q];
+        if (alias) { set_error("%s: an output buffer must not alias an input or another output", who); return PLX_ERR_INVALID; }
+    }
+    const int64_t cols = 2ll * nrhs * (1 + (L->built ? L->d : 0));
+    if (L->built && cols > kBackwardF64MaxCols) {
+        set_error("%s: nrhs = %d, d = %d is %lld stacked columns; the on-chip row of the contraction holds up to %d", who, nrhs,
+                  L->d, (long long)cols, kBackwardF64MaxCols);
+        return PLX_ERR_INVALID;
+    }
+    return check_f64(L, in[0], in[1], (int)cols, who);
+}
+
+int plx_backward_splat_f64(plx_lattice *L, const double *d_g, const double *d_src, const double *d_x, int nrhs,
+                           double *d_values, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_g, d_src, d_x}, *out[] = {d_values};
+    PLX_TRY(check_backward_f64(L, in, 3, out, 1, false, nrhs, "plx_backward_splat_f64"));
+    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_splat_f64"));
+    DeviceGuard g(L->device);
+    return backward_splat_f64_impl(L, d_g, d_src, d_x, nrhs, d_values, (hipStream_t)stream);
+}
+
+int plx_backward_contract_f64(plx_lattice *L, const double *d_values, const double *d_g, const double *d_src,
+                              const double *d_x, int nrhs, double *d_grad_x, double *d_grad_src, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_values, d_g, d_src, d_x}, *out[] = {d_grad_x, d_grad_src};
+    PLX_TRY(check_backward_f64(L, in, 4, out, 2, true, nrhs, "plx_backward_contract_f64"));
+    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_contract_f64"));
+    DeviceGuard g(L->device);
+    return backward_contract_f64_impl(L, d_values, d_g, d_src, d_x, nrhs, d_grad_x, d_grad_src, (hipStream_t)stream);
+}
+
+int plx_apply_backward_f64(plx_lattice *L, const double *d_g, const double *d_src, const double *d_x, int nrhs,
+                           double *d_grad_x, double *d_grad_src, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_g, d_src, d_x}, *out[] = {d_grad_x, d_grad_src};
+    PLX_TRY(check_backward_f64(L, in, 3, out, 2, true, nrhs, "plx_apply_backward_f64"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)L->m * 2 * nrhs * (1 + L->d) * 8;
+    PLX_TRY(ensure(L->val64_a, bytes));      // the workspace of plx_apply_f64
+    PLX_TRY(ensure(L->val64_b, bytes));
+    PLX_TRY(backward_splat_f64_impl(L, d_g, d_src, d_x, nrhs, L->val64_a.as<double>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), 2 * nrhs * (1 + L->d), &in_b, s));
+    return backward_contract_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), d_g, d_src, d_x, nrhs,
+                                      d_grad_x, d_grad_src, s);
+}
+
 int plx_apply_backward(plx_lattice *L, const float *d_g, const float *d_src, const float *d_ref, int nrhs,
                        float *d_grad_ref, float *d_grad_src, void *stream)
 {

@@ -1,0 +1,270 @@
+// plx_backward_f64.hip -- the float64 position gradient of out = K(x) src on a lattice built with the DERIVATIVE taps:
+// plx_backward_splat_f64 / plx_backward_contract_f64 / plx_apply_backward_f64 (include/plx.h; the entry points and their
+// argument checks are in plx_api.hip).  bilateral_kernel.py:113-123 in double without its two big matrices: the stacked
+// matrix [ g | g (x) x | src | src (x) x ] is formed inside the splat, the contraction of the filtered stack inside the
+// slice.  The blur between them is blur_f64_impl (plx_f64.hip), unchanged, at width C.
+//
+// L = nrhs columns, C = 2 L (1 + d) stack columns (always even), nch = C / 2 = L (1 + d) double2 chunks per value row.
+// Column c of the stack, tests/lattice64.py::stack64: h = L (1 + d); c < h comes from g, c >= h from src (c -= h); then
+// c < L is the plain column l = c, else the product column (l, k) = divmod(c - L, d): l-major.  x is the caller's float64
+// position matrix [n][d], not the float32 copy the lattice was built on.
+//
+// Kernels (256-thread workgroups, wave64), the chunk / wide shapes of plx_f64.hip:
+//   f64_backward_splat_chunk_kernel / f64_backward_splat_wide_kernel   f64_splat_chunk_kernel / f64_splat_wide_kernel with
+//       the source chunk formed on the fly: a lane decodes its two columns once, then per corner reads a = (g | src)[row][l]
+//       and, for a product column, x[row][k], forms the element as ONE rounded multiply a * x and accumulates
+//       fma((double)w, element, acc) in the corner order of f64_vertex_sum.
+//   f64_backward_contract_chunk_kernel / f64_backward_contract_wide_kernel   a lane group (a wave) per point in LATTICE order
+//       forms the point's filtered row with the sums of the fp64 slices -- d + 1 compiled in up to kGatherMaxD1, the run-time
+//       form above, one division by 1 + 2^-d -- and keeps it in LDS: 16 bytes per lane (chunk), nch * 16 bytes per wave
+//       (wide, dynamic).  A row never leaves its wave.  From the row, lane k < d of the group writes
+//           grad_x[row][k] = -2 sum_l ( s_l x_k wg_l - s_l wgx_lk + g_l x_k ws_l - g_l wsx_lk )
+//       with the sum taken for l ascending and the four terms in the order written, starting from 0, each product s_l x_k
+//       and g_l x_k formed first; lane l < L writes grad_src[row][l] = wg_l.  Both go to the caller's row through the
+//       point permutation.
+// The wide shape holds 4 rows of C doubles in the 64 KiB of LDS a workgroup may have: C <= kBackwardF64MaxCols = 2048.
+// Every output element is written by exactly one thread from sums in a fixed order: no atomics, bitwise reproducible.
+
+#include "plx_kernels.h"
+
+#include <math.h>
+
+namespace plx {
+
+// One column of the stack: where its factor a comes from, and k >= 0 for a product column a * x[k] (-1: the plain column).
+struct StackCol64 {
+    const double *a;
+    int l, k;
+};
+
+__device__ __forceinline__ StackCol64 stack_col64(int c, const double *__restrict__ g, const double *__restrict__ src, int L, int d)
+{
+    const int h = L * (1 + d);
+    StackCol64 s;
+    s.a = c < h ? g : src;
+    if (c >= h) c -= h;
+    if (c < L) {
+        s.l = c;
+        s.k = -1;
+    } else {
+        c -= L;
+        s.l = c / d;
+        s.k = c - s.l * d;
+    }
+    return s;
+}
+
+__device__ __forceinline__ double stack_elem64(const StackCol64 &s, const double *__restrict__ x, size_t row, int L, int d)
+{
+    const double a = s.a[row * L + s.l];
+    return s.k < 0 ? a : a * x[row * d + s.k];
+}
+
+// f64_vertex_sum over chunk ch of the stack rows: the same weights, the same corner order, the same fma
+__device__ __forceinline__ double2 stack_vertex_sum64(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
+                                                      const double *__restrict__ g, const double *__restrict__ src,
+                                                      const double *__restrict__ x, int L, int d, int ch)
+{
+    const StackCol64 c0 = stack_col64(2 * ch, g, src, L, d), c1 = stack_col64(2 * ch + 1, g, src, L, d);
+    double2 acc = VecOps<double2>::zero();
+    for (int j = j0; j < j1; ++j) {
+        const size_t r = (size_t)(row[j] & 0x7FFFFFFF);
+        VecOps<double2>::fma(acc, (double)w[j], make_double2(stack_elem64(c0, x, r, L, d), stack_elem64(c1, x, r, L, d)));
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(kBlock) void f64_backward_splat_chunk_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
+                                                                          const float *__restrict__ w, const double *__restrict__ g,
+                                                                          const double *__restrict__ src, const double *__restrict__ x,
+                                                                          int L, int d, int nch, int shift, int m,
+                                                                          double2 *__restrict__ values)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t v = t >> shift;
+    const int ch = (int)(t & ((1 << shift) - 1));
+    if (v >= m || ch >= nch) return;
+    values[(size_t)v * nch + ch] = stack_vertex_sum64(row, w, ptr[v], ptr[v + 1], g, src, x, L, d, ch);
+}
+
+__global__ __launch_bounds__(kBlock) void f64_backward_splat_wide_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
+                                                                         const float *__restrict__ w, const double *__restrict__ g,
+                                                                         const double *__restrict__ src, const double *__restrict__ x,
+                                                                         int L, int d, int nch, int m, double2 *__restrict__ values)
+{
+    const int64_t v = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (v >= m) return;
+    const int j0 = ptr[v], j1 = ptr[v + 1];
+    for (int ch = threadIdx.x & 63; ch < nch; ch += 64)
+        values[(size_t)v * nch + ch] = stack_vertex_sum64(row, w, j0, j1, g, src, x, L, d, ch);
+}
+
+// ---- slice + contraction -------------------------------------------------------------------------------------------
+// The corners of point p, read once per lane.  D1 > 0: d + 1 compiled in; 0: nothing is kept, the run-time form reads them.
+template <int D1> struct Corners64 {
+    int v[D1];
+    double w[D1];
+    __device__ __forceinline__ void load(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p)
+    {
+#pragma unroll
+        for (int r = 0; r < D1; ++r) v[r] = evid[(size_t)r * n + p];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) w[r] = (double)ew[(size_t)r * n + p];
+    }
+};
+template <> struct Corners64<0> {
+    __device__ __forceinline__ void load(const int *, const float *, int, int) {}
+};
+
+// chunk ch of the filtered row of point p: the sum of f64_slice_chunk_kernel (all gathers, then the ordered sum, one division)
+template <int D1>
+__device__ __forceinline__ double2 filtered_chunk64(const Corners64<D1> &c, const int *__restrict__ evid, const float *__restrict__ ew,
+                                                    int n, int p, int d1, const double2 *__restrict__ values, int nch, int ch,
+                                                    double denom)
+{
+    if constexpr (D1 > 0) {
+        double2 gath[D1];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) gath[r] = values[(size_t)c.v[r] * nch + ch];
+        double2 acc = VecOps<double2>::zero();
+#pragma unroll
+        for (int r = 0; r < D1; ++r) VecOps<double2>::fma(acc, c.w[r], gath[r]);
+        return make_double2(acc.x / denom, acc.y / denom);
+    } else {
+        return f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom);
+    }
+}
+
+// f: the point's filtered row [ wg | wgx | ws | wsx ] of C doubles in LDS.  Lane `lane` of `lanes` takes k = lane, lane +
+// lanes, ... and then l likewise: every output element has one writer.
+__device__ __forceinline__ void contract_row64(const double *f, int lane, int lanes, size_t row, const double *__restrict__ g,
+                                               const double *__restrict__ src, const double *__restrict__ x, int L, int d,
+                                               double *__restrict__ grad_x, double *__restrict__ grad_src)
+{
+    const int h = L * (1 + d);
+    for (int k = lane; k < d; k += lanes) {
+        const double xk = x[row * d + k];
+        double acc = 0.0;
+        for (int l = 0; l < L; ++l) {
+            const double s = src[row * L + l], gl = g[row * L + l];
+            acc += (s * xk) * f[l];
+            acc -= s * f[L + l * d + k];
+            acc += (gl * xk) * f[h + l];
+            acc -= gl * f[h + L + l * d + k];
+        }
+        grad_x[row * d + k] = -2.0 * acc;
+    }
+    if (grad_src)
+        for (int l = lane; l < L; l += lanes) grad_src[row * L + l] = f[l];
+}
+
+template <int D1>
+__global__ __launch_bounds__(kBlock) void f64_backward_contract_chunk_kernel(
+    const uint32_t *__restrict__ perm, const int *__restrict__ evid, const float *__restrict__ ew, int n, int d1,
+    const double2 *__restrict__ values, int nch, int shift, double denom, const double *__restrict__ g,
+    const double *__restrict__ src, const double *__restrict__ x, int L, int d, double *__restrict__ grad_x,
+    double *__restrict__ grad_src)
+{
+    __shared__ double2 rows[kBlock];                  // one chunk per lane; a group's row starts at its first lane
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t p64 = t >> shift;
+    const int ch = (int)(t & ((1 << shift) - 1));     // kBlock is a multiple of the group: also the lane's place in the group
+    const bool live = p64 < n;
+    const int p = live ? (int)p64 : 0;
+    if (live && ch < nch) {
+        Corners64<D1> c;
+        c.load(evid, ew, n, p);
+        rows[threadIdx.x] = filtered_chunk64<D1>(c, evid, ew, n, p, d1, values, nch, ch, denom);
+    }
+    __syncthreads();                                  // every thread of the workgroup arrives: nothing has returned yet
+    if (!live) return;
+    contract_row64(reinterpret_cast<const double *>(rows + (threadIdx.x - ch)), ch, 1 << shift, (size_t)perm[p], g, src, x, L,
+                   d, grad_x, grad_src);
+}
+
+template <int D1>
+__global__ __launch_bounds__(kBlock) void f64_backward_contract_wide_kernel(
+    const uint32_t *__restrict__ perm, const int *__restrict__ evid, const float *__restrict__ ew, int n, int d1,
+    const double2 *__restrict__ values, int nch, double denom, const double *__restrict__ g, const double *__restrict__ src,
+    const double *__restrict__ x, int L, int d, double *__restrict__ grad_x, double *__restrict__ grad_src)
+{
+    extern __shared__ double2 wide_rows[];            // kBlock / 64 rows of nch chunks, one per wave
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t p64 = (int64_t)blockIdx.x * (kBlock / 64) + wave;
+    const bool live = p64 < n;
+    const int p = live ? (int)p64 : 0;
+    double2 *mine = wide_rows + (size_t)wave * nch;
+    if (live) {
+        Corners64<D1> c;
+        c.load(evid, ew, n, p);
+        for (int ch = lane; ch < nch; ch += 64) mine[ch] = filtered_chunk64<D1>(c, evid, ew, n, p, d1, values, nch, ch, denom);
+    }
+    __syncthreads();
+    if (!live) return;
+    contract_row64(reinterpret_cast<const double *>(mine), lane, 64, (size_t)perm[p], g, src, x, L, d, grad_x, grad_src);
+}
+
+// ---- launch side ---------------------------------------------------------------------------------------------------
+// the vertex-sorted corners and their row pointer, as the fp64 splat of plx_f64.hip keeps them (the same generation mark)
+static int ensure_backward_tables(plx_lattice *L, hipStream_t stream)
+{
+    if (L->f64_gen == L->build_gen) return PLX_OK;
+    PLX_TRY(refuse_under_capture(stream, "the vertex row pointer of the float64 splat"));
+    PLX_TRY(export_row_ptr(L, stream));
+    L->f64_gen = L->build_gen;
+    return PLX_OK;
+}
+
+int backward_splat_f64_impl(plx_lattice *L, const double *d_g, const double *d_src, const double *d_x, int nrhs,
+                            double *d_values, hipStream_t stream)
+{
+    PLX_TRY(ensure_backward_tables(L, stream));
+    const int m = (int)L->m, d = L->d, nch = nrhs * (1 + d);
+    const int *ptr = L->row_ptr.as<int>(), *row = L->csr_row.as<int>();
+    const float *w = L->csr_w.as<float>();
+    double2 *v2 = reinterpret_cast<double2 *>(d_values);
+    if (nch <= kF64ChunkMax) {
+        L->kn_f64_splat = "f64_backward_splat_chunk_kernel";
+        const int shift = f64_group_shift(nch);
+        const int grid = ceil_div((int64_t)m << shift, kBlock);
+        f64_backward_splat_chunk_kernel<<<grid, kBlock, 0, stream>>>(ptr, row, w, d_g, d_src, d_x, nrhs, d, nch, shift, m, v2);
+    } else {
+        L->kn_f64_splat = "f64_backward_splat_wide_kernel";
+        const int grid = ceil_div(m, kBlock / 64);
+        f64_backward_splat_wide_kernel<<<grid, kBlock, 0, stream>>>(ptr, row, w, d_g, d_src, d_x, nrhs, d, nch, m, v2);
+    }
+    PLX_HIP_TRY(hipGetLastError());
+    return PLX_OK;
+}
+
+int backward_contract_f64_impl(plx_lattice *L, const double *d_values, const double *d_g, const double *d_src,
+                               const double *d_x, int nrhs, double *d_grad_x, double *d_grad_src, hipStream_t stream)
+{
+    const int n = (int)L->n, d = L->d, d1 = d + 1, nch = nrhs * (1 + d);
+    const double denom = 1.0 + ldexp(1.0, -d);
+    const uint32_t *perm = L->perm.as<uint32_t>();
+    const int *evid = L->evid.as<int>();
+    const float *ew = L->ew.as<float>();
+    const double2 *v2 = reinterpret_cast<const double2 *>(d_values);
+    if (nch <= kF64ChunkMax) {
+        L->kn_f64_slice = "f64_backward_contract_chunk_kernel";
+        const int shift = f64_group_shift(nch);
+        const int grid = ceil_div((int64_t)n << shift, kBlock);
+        dispatch_d1(d1, [&](auto D1) {
+            f64_backward_contract_chunk_kernel<decltype(D1)::value><<<grid, kBlock, 0, stream>>>(
+                perm, evid, ew, n, d1, v2, nch, shift, denom, d_g, d_src, d_x, nrhs, d, d_grad_x, d_grad_src);
+        });
+    } else {
+        L->kn_f64_slice = "f64_backward_contract_wide_kernel";
+        const int grid = ceil_div(n, kBlock / 64);
+        const size_t lds = (size_t)(kBlock / 64) * nch * sizeof(double2);      // <= 64 KiB: nch <= kBackwardF64MaxCols / 2
+        dispatch_d1(d1, [&](auto D1) {
+            f64_backward_contract_wide_kernel<decltype(D1)::value><<<grid, kBlock, lds, stream>>>(
+                perm, evid, ew, n, d1, v2, nch, denom, d_g, d_src, d_x, nrhs, d, d_grad_x, d_grad_src);
+        });
+    }
+    PLX_HIP_TRY(hipGetLastError());
+    return PLX_OK;
+}
+
+}  // namespace plx

@@ -392,6 +392,14 @@ int affine_f64_dot_rows(const plx_lattice *L, int vd);
 int slice_affine_f64_impl(plx_lattice *L, const double *d_values, int vd, const double *d_src, const double *d_ss,
                           double *d_out, double *d_partial, hipStream_t stream);
 int coldot_final_f64(const double *d_partial, int nrows, int stride, int vd, double *d_out, hipStream_t stream);
+// plx_backward_f64.hip: the float64 position gradient on the derivative-tap lattice -- the splat that forms the stacked
+// matrix [ g | g (x) x | src | src (x) x ] (2 nrhs (1 + d) columns) on the fly, and the slice with the contraction fused
+// (arguments checked by the entry points).  kBackwardF64MaxCols: the widest stack the on-chip row of the contraction holds.
+constexpr int kBackwardF64MaxCols = 2048;
+int backward_splat_f64_impl(plx_lattice *L, const double *d_g, const double *d_src, const double *d_x, int nrhs,
+                            double *d_values, hipStream_t stream);
+int backward_contract_f64_impl(plx_lattice *L, const double *d_values, const double *d_g, const double *d_src,
+                               const double *d_x, int nrhs, double *d_grad_x, double *d_grad_src, hipStream_t stream);
 // plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
 int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,

@@ -581,9 +581,25 @@ class Lattice:
         """True when plx_apply_backward covers this shape: 125..512 columns and 2*nrhs + d <= 62."""
         return 32 <= (2 * nrhs * (1 + d) + 3) // 4 <= 128 and 2 * nrhs + d <= 62
 
+    BACKWARD_F64_MAX_COLUMNS = 2048      # kBackwardF64MaxCols of plx_backward_f64.hip: the contraction's on-chip row
+
+    @staticmethod
+    def backward_f64_ok(nrhs, d):
+        """True when plx_apply_backward_f64 covers this shape: nrhs >= 1 and 2*nrhs*(1+d) <= 2048 stacked columns."""
+        return nrhs >= 1 and d >= 1 and 2 * nrhs * (1 + d) <= Lattice.BACKWARD_F64_MAX_COLUMNS
+
     def apply_backward(self, grad_out, src, ref, want_grad_src=True):
         """Position gradient of out = K(ref) src for a lattice built on `ref` with the DERIVATIVE taps
-        (bilateral_kernel.py:113-123), fused: returns (grad_ref [n, d], grad_src [n, nrhs] or None)."""
+        (bilateral_kernel.py:113-123), fused: returns (grad_ref [n, d], grad_src [n, nrhs] or None).  All three float64:
+        plx_apply_backward_f64 (the lattice is the one of `ref` rounded to float32, `ref` itself enters the stack and the
+        contraction in double; rows always in the caller's order; every shape backward_f64_ok names).  A mixed combination
+        is a TypeError."""
+        dtypes = {t.dtype for t in (grad_out, src, ref) if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise TypeError("grad_out, src and ref must all be float32 or all float64, got "
+                            + ", ".join(str(t.dtype) for t in (grad_out, src, ref) if isinstance(t, torch.Tensor)))
+        if dtypes == {torch.float64}:
+            return self._apply_backward_f64(grad_out, src, ref, want_grad_src)
         g = self._src(grad_out, self.n_owned)
         src = self._src(src, self.n_owned)
         ref = self._src(ref, self.n_owned)
@@ -598,6 +614,24 @@ class Lattice:
                                              ctypes.c_void_p(grad_src.data_ptr()) if want_grad_src else None,
                                              _stream_ptr(self.device))
         nv.check(rc, "plx_apply_backward")
+        return grad_ref, grad_src
+
+    def _apply_backward_f64(self, grad_out, src, ref, want_grad_src):
+        """The float64 form of apply_backward (plx_apply_backward_f64)."""
+        g = self._src(grad_out, self.n_owned, f64_ok=True)
+        src = self._src(src, self.n_owned, f64_ok=True)
+        ref = self._src(ref, self.n_owned, f64_ok=True)
+        if g.shape != src.shape or ref.shape[1] != self.d:
+            raise ValueError(f"Incompatible shapes {tuple(g.shape)}, {tuple(src.shape)}, {tuple(ref.shape)}")
+        grad_ref = torch.empty_like(ref)
+        grad_src = torch.empty_like(src) if want_grad_src else None
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_apply_backward_f64(self._h, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(src.data_ptr()),
+                                                 ctypes.c_void_p(ref.data_ptr()), src.shape[1],
+                                                 ctypes.c_void_p(grad_ref.data_ptr()),
+                                                 ctypes.c_void_p(grad_src.data_ptr()) if want_grad_src else None,
+                                                 _stream_ptr(self.device))
+        nv.check(rc, "plx_apply_backward_f64")
         return grad_ref, grad_src
 
     # -- introspection (parity tests) --------------------------------------

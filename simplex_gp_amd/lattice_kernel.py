@@ -227,6 +227,12 @@ class LatticeFilterGeneral(Function):
 
     method = None
     fused_backward = True      # False: position gradient through plx_backward_stack / filter / plx_backward_contract
+    # float64: True sends the position gradient of a CUDA 2-D double right-hand side through plx_apply_backward_f64 (stack
+    # formed inside the splat, contraction inside the slice; Lattice.backward_f64_ok shapes); False keeps the torch stack
+    # and contraction around the native fp64 product.  The two routes agree to rounding, so the
+    # switch changes time and memory only.  Off until the native route has been measured no slower than the torch route
+    # at the three shapes of tools/backward_f64_time.py (profiles/backward_f64_measured.md).
+    fused_backward_f64 = False
 
     @staticmethod
     def _filter():
@@ -255,14 +261,27 @@ class LatticeFilterGeneral(Function):
             if ctx.needs_input_grad[0] and not ctx.needs_input_grad[1]:
                 # K is treated as symmetric (py:110-111)
                 grad_source = filt(g.contiguous(), ref.contiguous(), ctx.coeffs)
-            # float32 only: the fused and the three-call position gradients are fp32 kernels.  In double the stack and the
+            # float32: the fused and the three-call position gradients are fp32 kernels.  In double the gradient is one
+            # native call too where fused_backward_f64 is on (plx_apply_backward_f64); otherwise the stack and the
             # contraction below are torch in float64 around the native fp64 product on the derivative-tap lattice.
             native = LatticeFilterGeneral.method is None and g.is_cuda and g.dim() == 2 and g.dtype == torch.float32
+            native64 = (LatticeFilterGeneral.fused_backward_f64 and LatticeFilterGeneral.method is None and g.is_cuda
+                        and g.dim() == 2 and g.dtype == src.dtype == ref.dtype == torch.float64
+                        and Lattice.backward_f64_ok(L, d))
+            lat64 = None
+            if ctx.needs_input_grad[1] and native64:
+                rc_ = ref if ref.is_contiguous() else carry_hint(ref.contiguous(), ref)
+                lat64 = _cache.get(rc_, ctx.deriv_coeffs)
+                if not lat64.accepts_rows():         # a sharded, merged or replayed build: the torch route serves it
+                    lat64 = None
             if ctx.needs_input_grad[1] and native and LatticeFilterGeneral.fused_backward and Lattice.backward_fusable(L, d):
                 # the whole of py:113-123 in one native call: the stacked matrix is never stored (plx_apply_backward)
                 rc_ = ref if ref.is_contiguous() else carry_hint(ref.contiguous(), ref)
                 lat = _cache.get(rc_, ctx.deriv_coeffs)
                 grad_reference, grad_source = lat.apply_backward(g, src, rc_, want_grad_src=ctx.needs_input_grad[0])
+            elif ctx.needs_input_grad[1] and lat64 is not None:
+                # the same in double: stack inside the splat, contraction inside the slice (plx_apply_backward_f64)
+                grad_reference, grad_source = lat64.apply_backward(g, src, rc_, want_grad_src=ctx.needs_input_grad[0])
             elif ctx.needs_input_grad[1] and native:
                 # same computation, the stack and the contraction each as one native pass (plx_backward_*)
                 import ctypes
