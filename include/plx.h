@@ -594,6 +594,45 @@ int plx_pcg_step_direction(float *d_p, const float *d_z, const float *d_rz_new, 
                            const float *d_active, const float *d_b_norm, float tol, int64_t n, int vd, float *d_beta,
                            float *d_active_out, void *stream);
 /*
+ * The same application in float64, next to the float64 CG solve (callers detect it by symbol; the version string is
+ * unchanged).  The factor is the one plx_pchol_* builds and STAYS fp32 (d_lt float [kp][ld] exactly as above: kp a multiple
+ * of 16 up to 1024, ld >= n a multiple of 64, zero tails, 16-byte aligned): an fp32 entry converts to double exactly, so
+ * P = L L^T + sigma^2 I is one matrix whatever precision applies it.  Everything else is double: vectors double [n][t]
+ * row-major (1 <= t <= 16, 8-byte aligned) in the SAME row order as the factor's n dimension, whatever that order is
+ * (solvers.LatticePreconditioner64 keeps both in the caller's order, like every fp64 call); G and T double [kp][16], of
+ * which a call writes columns 0..t-1; d_cinv double [kp][kp]; d_work plx_pcg_work_doubles(n, kp, t) doubles (-1 outside
+ * the limits above, monotone inside).
+ *   plx_pcg_gram_f64      G = L^T R: fp64 products of the converted entries with fp64 accumulation on the matrix cores
+ *                         (v_mfma_f64_16x16x4_f64), per-workgroup partial sums added in a fixed order.  With the factor's
+ *                         own columns as R (tiles of 16) it forms L^T L, hence C = sigma^2 I + L^T L, in double;
+ *   plx_pcg_project_f64   T = C^-1 (L^T R): the gram pass, then the kp x kp product with d_cinv in double;
+ *   plx_pcg_apply_f64     Z = (d_scale[0] R - L T) d_scale[1] (k <= kp = columns of L actually used: rows k.. of T are not
+ *                         read; d_scale two doubles in device memory) and, unless d_rz is NULL, d_rz[c] = <R[:, c], Z[:, c]>
+ *                         from the same registers, complete on return (one partial row per workgroup, fixed-order final
+ *                         sum).  d_z != d_r.  Rows of R and Z move as 16-byte pairs when t is even and both are 16-byte
+ *                         aligned;
+ *   plx_pcg_step_direction_f64   beta = active ? rz_new / max(rz, 1e-300) : 0; P = Z + beta P; active_out = active and
+ *                         sqrt(rr) / b_norm > tol: plx_cg_step_direction_f64 with Z as the source and the TRUE residual
+ *                         |R|^2 in the test (1 <= vd <= 256, every array double, active_out != active).
+ * plx_cg_step_update_f64 is used unchanged with rs := rz.  No allocation, no synchronisation (graph-capturable), no float
+ * atomics: two calls with the same arguments are bit-equal.  Every argument is checked before any launch: a NULL pointer,
+ * t or vd out of range, n < 1, k outside 0..kp, a factor off the shape contract, a pointer off its alignment and the
+ * aliasings named above are PLX_ERR_INVALID.
+ * Error bars (U = 2^-52; tests/test_pcg_f64_gpu.py): a gram entry (n + 4) U sum_i |L_ij R_ic|; a project entry
+ * (n + kp + 8) U sum_q |Cinv_jq| sum_i |L_iq R_ic|; an apply entry (k + 6) U |s1| (|s0 r| + sum_j |L_ij T_jc|); rz
+ * (n + 4) U sum_r |R Z|.
+ */
+int64_t plx_pcg_work_doubles(int64_t n, int kp, int t);
+int plx_pcg_gram_f64(const float *d_lt, int64_t ld, int kp, const double *d_r, int64_t n, int t, double *d_g, double *d_work,
+                     void *stream);
+int plx_pcg_project_f64(const float *d_lt, int64_t ld, int kp, const double *d_r, int64_t n, int t, const double *d_cinv,
+                        double *d_t, double *d_work, void *stream);
+int plx_pcg_apply_f64(const float *d_lt, int64_t ld, int kp, int k, const double *d_r, int64_t n, int t, const double *d_t,
+                      const double *d_scale, double *d_z, double *d_rz, double *d_work, void *stream);
+int plx_pcg_step_direction_f64(double *d_p, const double *d_z, const double *d_rz_new, const double *d_rz, const double *d_rr,
+                               const double *d_active, const double *d_b_norm, double tol, int64_t n, int vd, double *d_beta,
+                               double *d_active_out, void *stream);
+/*
  * The factor itself, built in batches of speculated pivots.  The sequential algorithm (GPyTorch's pivoted_cholesky, one
  * kernel row = one single-column MVM per pivot) is reproduced exactly, but nb <= 16 pivots share ONE nb-column MVM:
  *   plx_pchol_select        d_cand[0..nb) = the nb largest entries of the residual diagonal d_diag [n], ties by LOWER

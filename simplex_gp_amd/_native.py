@@ -115,6 +115,11 @@ _SIGNATURES = {
     "plx_pcg_apply": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plx_pcg_factor_to_half": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "plx_pcg_step_direction": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i64, _i32, _vp, _vp, _vp]),
+    "plx_pcg_work_doubles": (_i64, [_i64, _i32, _i32]),
+    "plx_pcg_gram_f64": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "plx_pcg_project_f64": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "plx_pcg_apply_f64": (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plx_pcg_step_direction_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i64, _i32, _vp, _vp, _vp]),
     "plx_pchol_work_bytes": (_i64, [_i64, _i32]),
     "plx_pchol_select": (_i32, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
     "plx_pchol_onehot": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp]),
@@ -134,6 +139,10 @@ _SIGNATURES = {
     "plx_reference_growth_info": (_i32, [_vp, ctypes.POINTER(_i64)]),
     "plx_apply_times": (_i32, [_vp, _f32p, _i32, ctypes.POINTER(_i32)]),
 }
+
+# Calls a library of this ABI may lack (features detected by symbol: has_symbols): lib() binds them where they exist.
+OPTIONAL_SYMBOLS = frozenset(("plx_pcg_work_doubles", "plx_pcg_gram_f64", "plx_pcg_project_f64", "plx_pcg_apply_f64",
+                              "plx_pcg_step_direction_f64"))
 
 
 def declared_symbols():
@@ -161,11 +170,19 @@ def lib():
             raise ImportError(f"{LIB_PATH} reports '{got}', these bindings need ABI {ABI_VERSION[0]}.{ABI_VERSION[1]}.x: "
                               "rebuild it with `make -C simplex_gp_amd/csrc` (or __graft_entry__.build())")
         for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)
+            fn = getattr(L, name, None) if name in OPTIONAL_SYMBOLS else getattr(L, name)
+            if fn is None:
+                continue
             fn.restype = res
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def has_symbols(*names):
+    """True when the loaded library exports every one of `names` (the optional calls of OPTIONAL_SYMBOLS)."""
+    L = lib()
+    return all(hasattr(L, name) for name in names)
 
 
 def check(rc, where):

@@ -492,6 +492,194 @@ class LatticePreconditioner:
         return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
 
 
+# The float64 preconditioned solve on the native double passes (plx_pcg_gram_f64, plx_pcg_project_f64, plx_pcg_apply_f64,
+# plx_pcg_step_direction_f64): True by default; False sends a double model back to PivotedCholeskyPreconditioner and the
+# torch loop (the A/B of tools/pcg_f64_time.py; profiles/pcg_f64_measured.md).
+NATIVE_PCG_F64 = True
+
+
+def _pcg_f64_available():
+    """The switch is on and the library exports the float64 preconditioner calls (they are detected by symbol)."""
+    if not NATIVE_PCG_F64:
+        return False
+    from . import _native as nv
+    return nv.has_symbols(*nv.OPTIONAL_SYMBOLS)
+
+
+class LatticePreconditioner64(LatticePreconditioner):
+    """LatticePreconditioner for a float64 model: the SAME factor, applied in double.
+
+    The factor is built by the fp32 batched route on the double model's lattice (the lattice of a float64 position tensor
+    serves fp32 right-hand sides) and stays stored in fp32 -- an fp32 entry converts to double exactly, and a
+    preconditioner only has to be SPD and the same matrix wherever it appears.  What differs from the fp32 class:
+      * rows are in the CALLER's order, like every fp64 call: the lattice-order factor is permuted once after the build
+        into a second [kp][ld] fp32 image (the lattice-order one is dropped), so neither solve() nor the native
+        iteration permutes anything;
+      * C = sigma^2 I + L^T L is formed in double by plx_pcg_gram_f64 itself, 16 factor columns at a time as the
+        right-hand side, so solve(), logdet() and sample() refer to one matrix P to double precision (the fp32 C the
+        base class forms on the way is discarded);
+      * solve() = plx_pcg_project_f64 + plx_pcg_apply_f64 on double vectors; a float32 R is a TypeError.
+    """
+
+    def __init__(self, lat, outputscale, noise, rank, rel_tol=1e-6, batch=16, sparse_rows=True, exact_steps=None):
+        from . import _native as nv
+        lib = nv.lib()
+        super().__init__(lat, outputscale, noise, rank, rel_tol=rel_tol, batch=batch, factor_dtype=torch.float32,
+                         sparse_rows=sparse_rows, exact_steps=exact_steps)
+        dev, n, k, kp, ld, noise = lat.device, self.n, self.rank, self.kp, self.ld, self.noise
+        rows = torch.zeros(kp, ld, dtype=torch.float32, device=dev)
+        rows[:, :n].index_copy_(1, lat.shard_perm(), self.Lt[:, :n])      # column perm[i] (caller row) <- lattice row i
+        self.Lt = self._factor = rows
+        self._work = {}
+        self._T = torch.zeros(kp, 16, dtype=torch.float64, device=dev)
+        C = torch.zeros(k, k, dtype=torch.float64, device=dev)
+        G = torch.empty(kp, 16, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            stream = _stream(dev)
+            for j0 in range(0, k, 16):
+                tb = min(16, k - j0)
+                R = rows[j0:j0 + tb, :n].t().double().contiguous()
+                nv.check(lib.plx_pcg_gram_f64(_vp(rows), ld, kp, _vp(R), n, tb, _vp(G), _vp(self._workspace(tb)), stream),
+                         "plx_pcg_gram_f64")
+                C[:, j0:j0 + tb] = G[:k, :tb]
+        self._C = C + noise * torch.eye(k, dtype=torch.float64, device=dev)
+        with _small_host_factorisation():
+            self._chol = torch.linalg.cholesky(self._C.cpu())
+            cinv = torch.eye(kp, dtype=torch.float64) / noise
+            cinv[:k, :k] = torch.cholesky_inverse(self._chol)
+        self._cinv = cinv.contiguous().to(dev)
+        self._logdet = float(2.0 * self._chol.diagonal().log().sum()) + (n - k) * math.log(noise)
+        self._scale_solve = torch.tensor([1.0, 1.0 / noise], dtype=torch.float64, device=dev)
+        self._scale_sample = torch.tensor([math.sqrt(noise), 1.0], dtype=torch.float64, device=dev)
+
+    @property
+    def L(self):
+        """[n, k] double, rows in the caller's order."""
+        return self._factor[:self.rank, :self.n].t().double().contiguous()
+
+    def _workspace(self, t):
+        from . import _native as nv
+        w = self._work.get(t)
+        if w is None:
+            w = self._work[t] = torch.empty(int(nv.lib().plx_pcg_work_doubles(self.n, self.kp, t)), dtype=torch.float64,
+                                            device=self._factor.device)
+        return w
+
+    def _check(self, R=None):
+        if R is not None and not (torch.is_tensor(R) and R.dtype == torch.float64):
+            raise TypeError("LatticePreconditioner64 takes float64 vectors, got %s"
+                            % (R.dtype if torch.is_tensor(R) else type(R).__name__))
+        if self.lat.build_id != self.build_id:
+            raise RuntimeError("LatticePreconditioner64: its lattice has been rebuilt for other positions (lattice-cache "
+                               "eviction); build the preconditioner again")
+
+    def solve_lattice(self, R, out=None, rz=None):
+        raise TypeError("LatticePreconditioner64 works on float64 vectors in the caller's row order: solve_rows()")
+
+    def _apply(self, R, T, scale, Z, rz):
+        from . import _native as nv
+        dev = self._factor.device
+        t = R.shape[1]
+        with torch.cuda.device(dev):
+            nv.check(nv.lib().plx_pcg_apply_f64(_vp(self._factor), self.ld, self.kp, self.rank, _vp(R), self.n, t, _vp(T), _vp(scale),
+                                                _vp(Z), _vp(rz), _vp(self._workspace(t)), _stream(dev)), "plx_pcg_apply_f64")
+        return Z
+
+    def solve_rows(self, R, out=None, rz=None):
+        """Z = P^-1 R for R [n, t] float64, rows in the caller's order (t <= 16); rz (optional, [t]) receives <R, Z> per
+        column."""
+        from . import _native as nv
+        self._check(R)
+        if not (R.is_cuda and R.dim() == 2 and R.is_contiguous() and R.shape[0] == self.n and 1 <= R.shape[1] <= 16):
+            raise ValueError(f"solve_rows takes a contiguous CUDA [{self.n}, 1..16] matrix, got {tuple(R.shape)}")
+        t = R.shape[1]
+        Z = torch.empty_like(R) if out is None else out
+        dev = self._factor.device
+        with torch.cuda.device(dev):
+            nv.check(nv.lib().plx_pcg_project_f64(_vp(self._factor), self.ld, self.kp, _vp(R), self.n, t, _vp(self._cinv),
+                                                  _vp(self._T), _vp(self._workspace(t)), _stream(dev)), "plx_pcg_project_f64")
+        return self._apply(R, self._T, self._scale_solve, Z, rz)
+
+    def solve(self, R):
+        """P^-1 R, rows in the caller's order (any number of float64 columns, in tiles of 16)."""
+        self._check(R)
+        outs = [self.solve_rows(R[:, c0:c0 + 16].contiguous()) for c0 in range(0, R.shape[1], 16)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+
+    def sample(self, t, generator=None):
+        """t float64 columns drawn from N(0, P): L g1 + sigma g2, the same draws in the same order as
+        PivotedCholeskyPreconditioner(dtype=torch.float64).sample."""
+        dev = self._factor.device
+        g1 = torch.randn(self.rank, t, generator=generator, device=dev, dtype=torch.float64)
+        g2 = torch.randn(self.n, t, generator=generator, device=dev, dtype=torch.float64)
+        self._check()
+        outs = []
+        for c0 in range(0, t, 16):
+            blk = g2[:, c0:c0 + 16].contiguous()
+            tb = blk.shape[1]
+            T = torch.zeros(self.kp, 16, dtype=torch.float64, device=dev)
+            T[:self.rank, :tb] = -g1[:, c0:c0 + tb]                      # Z = sigma g2 - L (-g1)
+            outs.append(self._apply(blk, T, self._scale_sample, torch.empty_like(blk), None))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+
+
+def _stream(dev):
+    import ctypes
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _batched_pcg_native_f64(matmul, B, precond, max_iter, tol, want_tridiag, check_every, matmul_dot=None, floor=0):
+    """_batched_pcg_native in double, rows in the caller's order, without the fused step forms: per iteration one MVM
+    (with its p^T A p where the product serves it), plx_cg_step_update_f64 (alpha = rz / pAp, X, R, |R|^2), the
+    preconditioner (plx_pcg_project_f64 + plx_pcg_apply_f64: Z = P^-1 R and <R, Z>) and plx_pcg_step_direction_f64."""
+    from . import _native as nv
+    lib = nv.lib()
+    n, t = B.shape
+    dev = B.device
+    X = torch.zeros_like(B)
+    R = B.clone().contiguous()
+    rz = torch.empty(t, dtype=torch.float64, device=dev)
+    rz_new = torch.empty_like(rz)
+    Z = precond.solve_rows(R, rz=rz)
+    P = Z.clone()
+    rz0 = rz.clone()
+    rr = _colsum(R, R)
+    b_norm = rr.sqrt().clamp_min(1e-300)
+    rr = rr.clone()
+    active = torch.ones(t, dtype=torch.float64, device=dev)
+    active_next = torch.empty_like(active)
+    work = _coldot_work(dev, t, torch.float64)
+    alphas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=torch.float64, device=dev)
+    betas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=torch.float64, device=dev)
+    it = 0
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        for it in range(1, max_iter + 1):
+            if matmul_dot is not None:
+                AP, pAp = matmul_dot(P)
+                pAp = pAp.contiguous()
+            else:
+                AP = matmul(P)
+                AP = AP if AP.is_contiguous() else AP.contiguous()
+                pAp = _colsum(P, AP)
+            row = it - 1 if want_tridiag else 0
+            nv.check(lib.plx_cg_step_update_f64(_vp(X), _vp(R), _vp(P), _vp(AP), _vp(rz), _vp(pAp), _vp(active), n, t, _vp(rr),
+                                                _vp(alphas[row]), _vp(work), stream), "plx_cg_step_update_f64")
+            precond.solve_rows(R, out=Z, rz=rz_new)
+            step_tol = float(tol) if it >= floor else min(float(tol), _FROZEN_BELOW)
+            nv.check(lib.plx_pcg_step_direction_f64(_vp(P), _vp(Z), _vp(rz_new), _vp(rz), _vp(rr), _vp(active), _vp(b_norm),
+                                                    step_tol, n, t, _vp(betas[row]), _vp(active_next), stream),
+                     "plx_pcg_step_direction_f64")
+            rz, rz_new = rz_new, rz
+            active, active_next = active_next, active
+            if tol > 0 and (it % check_every == 0 or it == max_iter) and not bool(active.any()):
+                break
+    info = {"iterations": it, "residual": (rr.sqrt() / b_norm), "rz0": rz0}
+    if want_tridiag:
+        info["tridiag"] = _tridiag_from_cg(alphas[:it], betas[:it], B, info)
+    return X, info
+
+
 def _batched_pcg_native(matmul, B, precond, max_iter, tol, want_tridiag, check_every, matmul_dot=None, floor=0):
     """Preconditioned batched CG on one GPU, rows in lattice order, scalars on the device: per iteration one MVM (with
     its p^T A p), plx_cg_step_update (alpha = rz / pAp, X, R, |R|^2), the preconditioner (plx_pcg_project +
@@ -933,7 +1121,7 @@ class LatticeGP(nn.Module):
         raw = getattr(self.kernel, "raw_lengthscale", None)
         parts = ([] if raw is None else [raw.detach().reshape(-1)]) + [self.raw_outputscale.detach().reshape(1),
                                                                      self.raw_noise.detach().reshape(1)]
-        return torch.cat([p.to(torch.float32) for p in parts])
+        return torch.cat([p.to(self.raw_noise.dtype) for p in parts])          # (a double model: compared in double)
 
     def _same_hyper(self, pre):
         snap = getattr(pre, "hyper_snapshot", None)
@@ -960,7 +1148,7 @@ class LatticeGP(nn.Module):
         if snap is None:
             return True
         k = raw.numel()
-        return snap.numel() == k + 2 and bool(torch.equal(snap[:k], raw.detach().reshape(-1).to(torch.float32)))
+        return snap.numel() == k + 2 and bool(torch.equal(snap[:k], raw.detach().reshape(-1).to(snap.dtype)))
 
     def __getstate__(self):
         # (copy.deepcopy / pickling of the module: the remembered preconditioner holds device handles of this process)
@@ -1040,7 +1228,10 @@ class LatticeGP(nn.Module):
         nothing is permuted and the lattice's row order is never touched; no column padding either (fp64 rows need 8-byte
         alignment only, and 16-byte accesses follow from an even column count).  Every MVM is plx_apply_affine_f64, with
         <P, AP> out of its slice kernel where the width allows."""
-        if cg_args.get("precond") is not None:
+        pre = cg_args.get("precond")
+        native_pre = isinstance(pre, LatticePreconditioner64) and NATIVE_PCG_F64 and pre.lat is lat \
+            and pre.build_id == lat.build_id and rhs.dim() == 2 and 1 <= rhs.shape[1] <= 16 and cg_args.get("reduce") is None
+        if pre is not None and not native_pre:
             # the caller-order branch of the fp32 solve: its factor's rows are in the caller's order too
             return batched_cg(lambda V: lat.apply(V).mul_(s).addcmul_(V, noise), rhs, **cg_args)
         ss = torch.stack([s.detach().reshape(()), noise.detach().reshape(())]).to(torch.float64).contiguous()
@@ -1049,6 +1240,16 @@ class LatticeGP(nn.Module):
         if lat.affine_dot_f64_ok(rhs.shape[1]):
             def fused_dot(V):
                 return lat.apply_affine(V, ss, want_dot=True)
+        if native_pre:
+            # the preconditioner's rows are in the caller's order like the product's: the native double iteration
+            # (batched_cg's arguments and defaults, bound through its own signature)
+            import inspect
+            a = inspect.signature(batched_cg).bind(None, rhs, **cg_args)
+            a.apply_defaults()
+            a = a.arguments
+            floor = _iteration_floor(a["max_iter"], a["want_tridiag"], a["min_iter"], a["min_tridiag_iter"])
+            return _batched_pcg_native_f64(lambda V: lat.apply_affine(V.contiguous(), ss), rhs, pre, a["max_iter"], a["tol"],
+                                           a["want_tridiag"], a["check_every"], fused_dot, floor)
         return batched_cg(lambda V: lat.apply_affine(V.contiguous(), ss), rhs, matmul_dot=fused_dot, **cg_args)
 
     def preconditioner(self, x, rank, K=None, factor_dtype=torch.float16):
@@ -1057,7 +1258,9 @@ class LatticeGP(nn.Module):
         from . import lattice_kernel as lk
         with torch.no_grad():
             # (the native passes hold at most LatticePreconditioner.MAX_RANK factor columns: larger ranks take the torch form)
-            if lk.LatticeFilterGeneral.method is None and x.is_cuda and x.dtype == torch.float32 \
+            f64 = x.dtype == torch.float64
+            if lk.LatticeFilterGeneral.method is None and x.is_cuda \
+                    and (x.dtype == torch.float32 or (f64 and _pcg_f64_available())) \
                     and min(int(rank), x.shape[0]) <= LatticePreconditioner.MAX_RANK:
                 ref = lk.carry_hint(K.x.detach(), K.x) if isinstance(K, lk.SquareLazyLattice) \
                     else lk.position_hint(x.div(self.kernel.lengthscale), x, scale_of=getattr(self.kernel, "raw_lengthscale", None))
@@ -1066,14 +1269,18 @@ class LatticeGP(nn.Module):
                 # the factor of the same operator again (an evaluation, then the next training step: the optimiser has not
                 # moved between them): the one built last, if nothing it depends on has been written since
                 last = self.__dict__.get("_last_preconditioner")
-                if last is not None and last.lat is lat and last.build_id == lat.build_id and last.asked == (int(rank), factor_dtype) \
+                # (a float64 x: the factor is stored in fp32 whatever factor_dtype says, and applied in double)
+                asked = (int(rank), torch.float64 if f64 else factor_dtype)
+                if last is not None and last.lat is lat and last.build_id == lat.build_id and last.asked == asked \
+                        and isinstance(last, LatticePreconditioner64) == f64 \
                         and self._same_positions(last, x) and self._same_hyper(last):
                     self.preconditioner_reuses = self.__dict__.get("preconditioner_reuses", 0) + 1
                     return last
-                pre = LatticePreconditioner(lat, self.outputscale, self.noise, rank, factor_dtype=factor_dtype)
+                pre = LatticePreconditioner64(lat, self.outputscale, self.noise, rank) if f64 \
+                    else LatticePreconditioner(lat, self.outputscale, self.noise, rank, factor_dtype=factor_dtype)
                 pre.ref = ref          # the positions its lattice was built on (kept alive: the lattice-cache key)
                 pre.ref_key = self._positions_key(x)
-                pre.asked = (int(rank), factor_dtype)
+                pre.asked = asked
                 pre.hyper_snapshot, pre.min_noise = self._hyper_snapshot(), float(self.min_noise)
                 self.__dict__["_last_preconditioner"] = pre
                 return pre
