@@ -525,6 +525,27 @@ int plx_lanczos_max_rows(void);
 int64_t plx_lanczos_work_floats(int64_t n);
 int plx_lanczos_step(float *d_q, int64_t ld, float *d_w, int64_t n, int i, float *d_alphas, float *d_betas, float *d_work,
                      void *stream);
+/*
+ * The same step with every array in double (csrc/plx_lanczos_f64.hip): the recurrence and its order are
+ * plx_lanczos_step's, the guard of the division is 1e-300 (row i + 1 of d_q = w / max(beta_i, 1e-300)).
+ *   d_q       double [rows >= i + 2][ld], row-major, 16-byte aligned, ld >= n and ld % 2 == 0; columns n..ld-1 are never
+ *             read for a result and never written
+ *   d_w       double [n]: A q_i on entry, overwritten with the re-orthogonalised, un-normalised vector.  It must not
+ *             overlap rows 0..i+1 of the basis, [d_q, d_q + (i + 2) ld)
+ *   d_work    double [plx_lanczos_work_doubles(n)] (-1: n < 1 or more than the 2,097,152 rows the step serves)
+ * Writes d_alphas[i], d_betas[i] and row i + 1 of d_q, and nothing else outside d_work.  Never allocates, never
+ * synchronises (graph-capturable); deterministic: every sum is taken in a fixed order, no atomics.  i + 1 <=
+ * plx_lanczos_max_rows() (256).  Every argument is checked before any launch; PLX_ERR_INVALID (plx_last_error names the
+ * call): a NULL pointer, a pointer off 8-byte alignment or d_q off 16-byte alignment, an odd ld or ld < n, n < 1, i < 0 or
+ * i + 1 > 256, an n the step does not serve, d_w overlapping the basis rows above.
+ * plx_lanczos_shape_f64 (host only, no device): the rows per workgroup (span) and the workgroup count (groups =
+ * ceil(n / span)) the step uses for n -- what plx_exact_splits is for the exact MVM: where the kernel shape changes,
+ * without restating the rule.  PLX_ERR_INVALID where plx_lanczos_work_doubles refuses; span or groups may be NULL.
+ */
+int64_t plx_lanczos_work_doubles(int64_t n);
+int plx_lanczos_shape_f64(int64_t n, int *span, int *groups);
+int plx_lanczos_step_f64(double *d_q, int64_t ld, double *d_w, int64_t n, int i, double *d_alphas, double *d_betas,
+                         double *d_work, void *stream);
 /* The two vector updates of a batched CG iteration, one pass each (row-major [n][vd], per-column scalars on the
  * device):  plx_cg_update: X += P*alpha, R -= AP*alpha, d_rs_new[c] = sum_r R[r][c]^2 (d_work as for plx_coldot);
  *           plx_cg_direction: P = R + P*beta. */

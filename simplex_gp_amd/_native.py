@@ -102,6 +102,9 @@ _SIGNATURES = {
     "plx_lanczos_max_rows": (_i32, []),
     "plx_lanczos_work_floats": (_i64, [_i64]),
     "plx_lanczos_step": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "plx_lanczos_work_doubles": (_i64, [_i64]),
+    "plx_lanczos_shape_f64": (_i32, [_i64, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "plx_lanczos_step_f64": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "plx_cg_step_update": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "plx_cg_step_direction": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i64, _i32, _vp, _vp, _vp]),
     "plx_cg_update": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
@@ -142,7 +145,8 @@ _SIGNATURES = {
 
 # Calls a library of this ABI may lack (features detected by symbol: has_symbols): lib() binds them where they exist.
 OPTIONAL_SYMBOLS = frozenset(("plx_pcg_work_doubles", "plx_pcg_gram_f64", "plx_pcg_project_f64", "plx_pcg_apply_f64",
-                              "plx_pcg_step_direction_f64"))
+                              "plx_pcg_step_direction_f64", "plx_lanczos_work_doubles", "plx_lanczos_shape_f64",
+                              "plx_lanczos_step_f64"))
 
 
 def declared_symbols():

@@ -97,37 +97,47 @@ def _lanczos_replayed(matmul, v0, steps, check_every, capture=True):
 
 LANCZOS_NATIVE = True         # on a GPU in fp32: re-orthogonalisation, coefficients and the next basis vector as four launches
 #                               of libplx (plx_lanczos_step) instead of ~19 torch launches per step
+LANCZOS_NATIVE_F64 = True     # the same for a float64 v0 (plx_lanczos_step_f64); False: a double v0 takes the torch forms
+_F64_SYMBOLS = ("plx_lanczos_work_doubles", "plx_lanczos_shape_f64", "plx_lanczos_step_f64")
 
 
 def _lanczos_native(matmul, v0, steps, check_every):
-    """The recurrence with everything but the MVM in plx_lanczos_step (csrc/plx_lanczos.hip): per step the operator's own
-    launches + 4.  The components along q_{i-1}, q_i first (the three-term recurrence), then one classical Gram-Schmidt
-    pass against the whole basis built so far -- the torch form's order, which is what keeps the pass stable;
-    deterministic.  None when the library does not serve this shape
-    (more than 256 steps or 2,097,152 rows)."""
+    """The recurrence with everything but the MVM in plx_lanczos_step (csrc/plx_lanczos.hip) or, for a float64 v0,
+    plx_lanczos_step_f64 (csrc/plx_lanczos_f64.hip): per step the operator's own launches + 4.  The components along
+    q_{i-1}, q_i first (the three-term recurrence), then one classical Gram-Schmidt pass against the whole basis built so
+    far -- the torch form's order, which is what keeps the pass stable; deterministic.  Basis, coefficients and
+    workspace are in v0.dtype; the rows of the basis start on 256-byte boundaries.  None when the library does not serve
+    this shape (more than 256 steps or 2,097,152 rows), or, for float64, lacks the calls."""
     import ctypes
     from . import _native as nv
-    lib = nv.lib()
-    n, dev = v0.shape[0], v0.device
-    work_floats = int(lib.plx_lanczos_work_floats(n))
-    if steps > int(lib.plx_lanczos_max_rows()) or work_floats < 0:
+    n, dev, dt = v0.shape[0], v0.device, v0.dtype
+    if dt == torch.float64:
+        if not nv.has_symbols(*_F64_SYMBOLS):
+            return None
+        lib = nv.lib()
+        work_size, step, name, pad = lib.plx_lanczos_work_doubles, lib.plx_lanczos_step_f64, "plx_lanczos_step_f64", 32
+    else:
+        lib = nv.lib()
+        work_size, step, name, pad = lib.plx_lanczos_work_floats, lib.plx_lanczos_step, "plx_lanczos_step", 64
+    work_count = int(work_size(n))
+    if steps > int(lib.plx_lanczos_max_rows()) or work_count < 0:
         return None
-    ld = (n + 63) // 64 * 64                                                 # rows of the basis start on 256-byte boundaries
-    Qb = torch.zeros(steps + 1, ld, dtype=torch.float32, device=dev)         # one spare row: the last step writes q_steps
-    alphas = torch.zeros(steps, dtype=torch.float32, device=dev)
-    betas = torch.zeros(steps, dtype=torch.float32, device=dev)
-    work = torch.empty(work_floats, dtype=torch.float32, device=dev)
+    ld = (n + pad - 1) // pad * pad                                          # rows of the basis start on 256-byte boundaries
+    Qb = torch.zeros(steps + 1, ld, dtype=dt, device=dev)                    # one spare row: the last step writes q_steps
+    alphas = torch.zeros(steps, dtype=dt, device=dev)
+    betas = torch.zeros(steps, dtype=dt, device=dev)
+    work = torch.empty(work_count, dtype=dt, device=dev)
     Qb[0, :n] = v0 / v0.norm()
     t = None
     with torch.cuda.device(dev):
         for i in range(steps):
             w = matmul(Qb[i, :n].unsqueeze(-1)).reshape(n)
-            if not w.is_contiguous() or w.dtype != torch.float32 or w.data_ptr() == Qb[i].data_ptr():
-                w = w.to(torch.float32).contiguous().clone()                 # (the step overwrites w: never the basis row itself)
+            if not w.is_contiguous() or w.dtype != dt or w.data_ptr() == Qb[i].data_ptr():
+                w = w.to(dt).contiguous().clone()                            # (the step overwrites w: never the basis row itself)
             stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            nv.check(lib.plx_lanczos_step(ctypes.c_void_p(Qb.data_ptr()), ld, ctypes.c_void_p(w.data_ptr()), n, i,
-                                          ctypes.c_void_p(alphas.data_ptr()), ctypes.c_void_p(betas.data_ptr()),
-                                          ctypes.c_void_p(work.data_ptr()), stream), "plx_lanczos_step")
+            nv.check(step(ctypes.c_void_p(Qb.data_ptr()), ld, ctypes.c_void_p(w.data_ptr()), n, i,
+                          ctypes.c_void_p(alphas.data_ptr()), ctypes.c_void_p(betas.data_ptr()),
+                          ctypes.c_void_p(work.data_ptr()), stream), name)
             if (i + 1) % check_every == 0 and i + 1 < steps:
                 t = _first_breakdown(alphas, betas, i + 1)
                 if t is not None:
@@ -142,18 +152,20 @@ def lanczos(matmul, v0, steps, check_every=8, graph=None, native=None):
     """`steps` Lanczos iterations with full re-orthogonalisation.
     Returns Q [n, t] (orthonormal) and the tridiagonal T [t, t] with Q^T A Q = T.
 
-    On a GPU in fp32 (native, default LANCZOS_NATIVE): everything around the MVM is plx_lanczos_step -- four launches per
-    step (_lanczos_native).  Otherwise torch ops: the basis lives in one preallocated [steps, n] buffer (stacking the
+    On a GPU in fp32 (native, default LANCZOS_NATIVE) or in float64 (default LANCZOS_NATIVE_F64): everything around the
+    MVM is plx_lanczos_step / plx_lanczos_step_f64 -- four launches per step (_lanczos_native).  Otherwise torch ops: the
+    basis lives in one preallocated [steps, n] buffer (stacking the
     vectors anew in every step copied O(steps^2 n) bytes) and the breakdown test -- beta below 1e-6 |alpha_0|: the
     Krylov space is exhausted -- reads the device every `check_every` steps instead of twice per step; vectors produced
     after a breakdown are discarded when it is found.
     graph (default LANCZOS_GRAPH; looked at when the native step is off or does not serve the shape): the torch step
     captured once into a HIP graph and replayed (_lanczos_replayed); `matmul` must then be capturable -- no host
     read-backs, no allocations outside torch's pool: the operators of this package are, once their lattice is built.  A
-    refused capture falls back to the eager loop (the reason is kept in _graph_refusals)."""
-    if native is None:
-        native = LANCZOS_NATIVE and graph is None                   # (an explicit graph=True / False asks for a torch form)
-    if native and v0.is_cuda and v0.dtype == torch.float32 and not torch.cuda.is_current_stream_capturing():
+    refused capture falls back to the eager loop (the reason is kept in _graph_refusals).
+    native=True with a dtype other than float32 or float64 falls through to the torch forms."""
+    if native is None:                                                  # (an explicit graph=True / False asks for a torch form)
+        native = (LANCZOS_NATIVE_F64 if v0.dtype == torch.float64 else LANCZOS_NATIVE) and graph is None
+    if native and v0.is_cuda and v0.dtype in (torch.float32, torch.float64) and not torch.cuda.is_current_stream_capturing():
         out = _lanczos_native(matmul, v0, steps, max(int(check_every), 32))
         if out is not None:
             return out
