@@ -8,6 +8,8 @@
 // consecutive threads read consecutive doubles -- a 64-lane wave covers 512 consecutive bytes whatever vd is, and a
 // power-of-two lane count per row would idle 5 of 16 lanes at vd = 11.  Per-workgroup partial sums through LDS in a fixed
 // order, then one workgroup per column adds the partial rows in a fixed order: no atomics, bitwise reproducible.
+// The preconditioned iteration shares this file's steps (plx_internal.h): its <R, Z> is summed by coldot_final_f64, its
+// direction step is step_direction_f64, and plx_pcg_f64.hip checks its pointers with check_cg64.
 //
 // The affine slice is plx_f64.hip's slice (the same three shapes, the same gates, the sums formed from the same pieces
 // of plx_kernels.h in the same order, ONE division by 1 + 2^-d) with the tail out = fma(a, y, b x) fused: the slice already
@@ -18,8 +20,6 @@
 #include "plx_kernels.h"
 
 #include <math.h>
-
-#include <initializer_list>
 
 namespace plx {
 
@@ -83,8 +83,6 @@ __global__ __launch_bounds__(kFinal64Block) void coldot64_final_kernel(const dou
 }
 
 //   step_update:     alpha = active ? rs / max(pAp, tiny) : 0;  X += alpha P;  R -= alpha AP;  partial |R|^2
-//   step_direction:  beta = active ? rs_new / max(rs, tiny) : 0;  P = R + beta P;
-//                    active' = active and sqrt(rs_new) / b_norm > tol
 __global__ __launch_bounds__(kBlock) void cg64_step_update_kernel(double *__restrict__ X, double *__restrict__ R,
                                                                   const double *__restrict__ P, const double *__restrict__ AP,
                                                                   const double *__restrict__ rs, const double *__restrict__ pAp,
@@ -115,55 +113,60 @@ __global__ __launch_bounds__(kBlock) void cg64_step_update_kernel(double *__rest
     cg64_store_partial(red, c, rl, cw, vd, rows_per_step, partial);
 }
 
-__device__ __forceinline__ double cg64_beta(const double *rs_new, const double *rs, const double *active, int c)
+// The direction step of a plain and of a preconditioned iteration: P = src + beta P, beta = active ? num / max(den, tiny) : 0,
+// active' = active and sqrt(rr) / b_norm > tol.  CG: src = R, num = rr = |R'|^2, den = |R|^2 (num and rr are then one
+// read-only pointer); PCG: src = Z, num = <R', Z'>, den = <R, Z>, rr = the true |R'|^2.
+__device__ __forceinline__ double direction64_beta(const double *num, const double *den, const double *active, int c)
 {
-    return active[c] > 0.0 ? rs_new[c] / fmax(rs[c], kTiny64) : 0.0;
+    return active[c] > 0.0 ? num[c] / fmax(den[c], kTiny64) : 0.0;
 }
 
-__device__ __forceinline__ void cg64_direction_scalars(const double *rs_new, const double *rs, const double *active,
-                                                       const double *b_norm, double tol, int vd, double *beta_out,
-                                                       double *active_out)
+__device__ __forceinline__ void direction64_scalars(const double *num, const double *den, const double *rr,
+                                                    const double *active, const double *b_norm, double tol, int vd,
+                                                    double *beta_out, double *active_out)
 {
     if (blockIdx.x == 0 && (int)threadIdx.x < vd) {
         const int c = threadIdx.x;
-        beta_out[c] = cg64_beta(rs_new, rs, active, c);
-        active_out[c] = (active[c] > 0.0 && sqrt(rs_new[c]) / b_norm[c] > tol) ? 1.0 : 0.0;
+        beta_out[c] = direction64_beta(num, den, active, c);
+        active_out[c] = (active[c] > 0.0 && sqrt(rr[c]) / b_norm[c] > tol) ? 1.0 : 0.0;
     }
 }
 
 // beta per column once per workgroup; the column of element i = blockIdx * kBlock + tid from 32-bit residues
-__global__ __launch_bounds__(kBlock) void cg64_step_direction_kernel(double *__restrict__ P, const double *__restrict__ R,
-                                                                     const double *__restrict__ rs_new,
-                                                                     const double *__restrict__ rs,
-                                                                     const double *__restrict__ active,
-                                                                     const double *__restrict__ b_norm, double tol,
-                                                                     int64_t total, int vd, double *__restrict__ beta_out,
-                                                                     double *__restrict__ active_out)
+__global__ __launch_bounds__(kBlock) void step_direction64_kernel(double *__restrict__ P, const double *__restrict__ src,
+                                                                  const double *__restrict__ num,
+                                                                  const double *__restrict__ den,
+                                                                  const double *__restrict__ rr,
+                                                                  const double *__restrict__ active,
+                                                                  const double *__restrict__ b_norm, double tol,
+                                                                  int64_t total, int vd, double *__restrict__ beta_out,
+                                                                  double *__restrict__ active_out)
 {
     __shared__ double sbeta[kBlock];
-    if ((int)threadIdx.x < vd) sbeta[threadIdx.x] = cg64_beta(rs_new, rs, active, threadIdx.x);
+    if ((int)threadIdx.x < vd) sbeta[threadIdx.x] = direction64_beta(num, den, active, threadIdx.x);
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < total) {
         const uint32_t uvd = (uint32_t)vd;
         const uint32_t bm = ((blockIdx.x % uvd) * ((uint32_t)kBlock % uvd)) % uvd;      // wave-uniform
         const uint32_t c = (bm + threadIdx.x) % uvd;
-        P[i] = R[i] + P[i] * sbeta[c];
+        P[i] = src[i] + P[i] * sbeta[c];
     }
-    cg64_direction_scalars(rs_new, rs, active, b_norm, tol, vd, beta_out, active_out);
+    direction64_scalars(num, den, rr, active, b_norm, tol, vd, beta_out, active_out);
 }
 
-// the same two elements per thread (16-byte loads / stores; total even, P and R 16-byte aligned)
-__global__ __launch_bounds__(kBlock) void cg64_step_direction2_kernel(double2 *__restrict__ P, const double2 *__restrict__ R,
-                                                                      const double *__restrict__ rs_new,
-                                                                      const double *__restrict__ rs,
-                                                                      const double *__restrict__ active,
-                                                                      const double *__restrict__ b_norm, double tol,
-                                                                      int64_t pairs, int vd, double *__restrict__ beta_out,
-                                                                      double *__restrict__ active_out)
+// the same two elements per thread (16-byte loads / stores; total even, P and src 16-byte aligned)
+__global__ __launch_bounds__(kBlock) void step_direction64_pair_kernel(double2 *__restrict__ P, const double2 *__restrict__ src,
+                                                                       const double *__restrict__ num,
+                                                                       const double *__restrict__ den,
+                                                                       const double *__restrict__ rr,
+                                                                       const double *__restrict__ active,
+                                                                       const double *__restrict__ b_norm, double tol,
+                                                                       int64_t pairs, int vd, double *__restrict__ beta_out,
+                                                                       double *__restrict__ active_out)
 {
     __shared__ double sbeta[kBlock];
-    if ((int)threadIdx.x < vd) sbeta[threadIdx.x] = cg64_beta(rs_new, rs, active, threadIdx.x);
+    if ((int)threadIdx.x < vd) sbeta[threadIdx.x] = direction64_beta(num, den, active, threadIdx.x);
     __syncthreads();
     const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (q < pairs) {
@@ -171,13 +174,13 @@ __global__ __launch_bounds__(kBlock) void cg64_step_direction2_kernel(double2 *_
         // column of element 2 q = 2 (blockIdx kBlock + tid) mod vd, from 32-bit residues
         const uint32_t bm = ((blockIdx.x % uvd) * ((2u * (uint32_t)kBlock) % uvd)) % uvd;      // wave-uniform
         uint32_t c = (bm + 2u * threadIdx.x) % uvd;
-        const double2 r = R[q];
+        const double2 r = src[q];
         double2 p = P[q];
         p.x = r.x + p.x * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
         p.y = r.y + p.y * sbeta[c];
         P[q] = p;
     }
-    cg64_direction_scalars(rs_new, rs, active, b_norm, tol, vd, beta_out, active_out);
+    direction64_scalars(num, den, rr, active, b_norm, tol, vd, beta_out, active_out);
 }
 
 // ---- the slice with the affine tail ----------------------------------------------------------------------------------------
@@ -371,12 +374,8 @@ int slice_affine_f64_impl(plx_lattice *L, const double *d_values, int vd, const 
     return PLX_OK;
 }
 
-}  // namespace plx
-
-using namespace plx;
-
 // Everything a vector call checks before any launch.  ptrs: every pointer argument of the call.
-static int check_cg64(const char *who, std::initializer_list<const void *> ptrs, int64_t n, int vd)
+int check_cg64(const char *who, std::initializer_list<const void *> ptrs, int64_t n, int vd)
 {
     uintptr_t bits = 0;
     for (const void *q : ptrs) {
@@ -388,6 +387,30 @@ static int check_cg64(const char *who, std::initializer_list<const void *> ptrs,
     if ((bits & 7) != 0) { set_error("%s: buffers of doubles must be 8-byte aligned", who); return PLX_ERR_INVALID; }
     return PLX_OK;
 }
+
+int step_direction_f64(const char *who, double *d_p, const double *d_src, const double *d_num, const double *d_den,
+                       const double *d_rr, const double *d_active, const double *d_b_norm, double tol, int64_t n, int vd,
+                       double *d_beta, double *d_active_out, hipStream_t s)
+{
+    PLX_TRY(check_cg64(who, {d_p, d_src, d_num, d_den, d_rr, d_active, d_b_norm, d_beta, d_active_out}, n, vd));
+    if (d_active == d_active_out) { set_error("%s: active and active_out must be different buffers", who); return PLX_ERR_INVALID; }
+    const int64_t total = n * vd;
+    if ((total & 1) == 0 && ((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_src)) & 15) == 0) {
+        const int64_t pairs = total / 2;
+        step_direction64_pair_kernel<<<ceil_div(pairs, kBlock), kBlock, 0, s>>>(
+            reinterpret_cast<double2 *>(d_p), reinterpret_cast<const double2 *>(d_src), d_num, d_den, d_rr, d_active, d_b_norm,
+            tol, pairs, vd, d_beta, d_active_out);
+    } else {
+        step_direction64_kernel<<<ceil_div(total, kBlock), kBlock, 0, s>>>(d_p, d_src, d_num, d_den, d_rr, d_active, d_b_norm, tol,
+                                                                          total, vd, d_beta, d_active_out);
+    }
+    PLX_HIP_TRY(hipGetLastError());
+    return PLX_OK;
+}
+
+}  // namespace plx
+
+using namespace plx;
 
 extern "C" int64_t plx_coldot_work_doubles(int vd) { return (vd >= 1 && vd <= kBlock) ? (int64_t)kDot64Blocks * vd : -1; }
 
@@ -418,22 +441,6 @@ extern "C" int plx_cg_step_direction_f64(double *d_p, const double *d_r, const d
                                          const double *d_active, const double *d_b_norm, double tol, int64_t n, int vd,
                                          double *d_beta, double *d_active_out, void *stream)
 {
-    PLX_TRY(check_cg64("plx_cg_step_direction_f64", {d_p, d_r, d_rs_new, d_rs, d_active, d_b_norm, d_beta, d_active_out}, n, vd));
-    if (d_active == d_active_out) {
-        set_error("plx_cg_step_direction_f64: active and active_out must be different buffers");
-        return PLX_ERR_INVALID;
-    }
-    const int64_t total = n * vd;
-    hipStream_t s = (hipStream_t)stream;
-    if ((total & 1) == 0 && ((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_r)) & 15) == 0) {
-        const int64_t pairs = total / 2;
-        cg64_step_direction2_kernel<<<ceil_div(pairs, kBlock), kBlock, 0, s>>>(
-            reinterpret_cast<double2 *>(d_p), reinterpret_cast<const double2 *>(d_r), d_rs_new, d_rs, d_active, d_b_norm, tol,
-            pairs, vd, d_beta, d_active_out);
-    } else {
-        cg64_step_direction_kernel<<<ceil_div(total, kBlock), kBlock, 0, s>>>(d_p, d_r, d_rs_new, d_rs, d_active, d_b_norm, tol,
-                                                                             total, vd, d_beta, d_active_out);
-    }
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
+    return step_direction_f64("plx_cg_step_direction_f64", d_p, d_r, d_rs_new, d_rs, d_rs_new, d_active, d_b_norm, tol, n, vd,
+                              d_beta, d_active_out, (hipStream_t)stream);
 }

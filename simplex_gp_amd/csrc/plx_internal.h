@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <initializer_list>
+
 #include "plx.h"
 
 namespace plx {
@@ -392,6 +394,13 @@ int affine_f64_dot_rows(const plx_lattice *L, int vd);
 int slice_affine_f64_impl(plx_lattice *L, const double *d_values, int vd, const double *d_src, const double *d_ss,
                           double *d_out, double *d_partial, hipStream_t stream);
 int coldot_final_f64(const double *d_partial, int nrows, int stride, int vd, double *d_out, hipStream_t stream);
+// plx_cg_f64.hip, shared with plx_pcg_f64.hip: what every float64 vector call checks before any launch (ptrs: every pointer
+// argument: non-NULL, 8-byte aligned; 1 <= vd <= kBlock, n >= 1; `who` prefixes the error text), and the direction step of
+// plx_cg_step_direction_f64 (src = R, num = rr = |R'|^2, den = |R|^2) and plx_pcg_step_direction_f64, arguments checked
+int check_cg64(const char *who, std::initializer_list<const void *> ptrs, int64_t n, int vd);
+int step_direction_f64(const char *who, double *d_p, const double *d_src, const double *d_num, const double *d_den,
+                       const double *d_rr, const double *d_active, const double *d_b_norm, double tol, int64_t n, int vd,
+                       double *d_beta, double *d_active_out, hipStream_t stream);
 // plx_backward_f64.hip: the float64 position gradient on the derivative-tap lattice -- the splat that forms the stacked
 // matrix [ g | g (x) x | src | src (x) x ] (2 nrhs (1 + d) columns) on the fly, and the slice with the contraction fused
 // (arguments checked by the entry points).  kBackwardF64MaxCols: the widest stack the on-chip row of the contraction holds.

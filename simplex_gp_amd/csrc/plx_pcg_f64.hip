@@ -9,13 +9,13 @@
 //                         entries (24 x 53 bits is rounded once, by the fma), fp64 accumulation
 //   pcg64_project_kernel  the partials in workgroup order, then (plx_pcg_project_f64) T = C^-1 G with C^-1 fp64 [kp][kp]
 //   pcg64_apply_kernel    Z = (in_scale R - L T) out_scale, one row per lane, and the workgroup's partial <R, Z>
-//   pcg64_step_direction  beta = rz' / rz, P = Z + beta P, active' from the TRUE residual norm
+// <R, Z> is summed from the apply partials by plx_cg_f64.hip's coldot_final_f64, and plx_pcg_step_direction_f64 (beta =
+// rz' / rz, P = Z + beta P, active' from the TRUE residual norm) is its step_direction_f64.
 // Vectors are double [n][t], rows in whatever order the factor's n dimension is in (solvers.LatticePreconditioner64 keeps
 // both in the caller's order, like every fp64 call).  No atomics: partial sums per workgroup, fixed-order final sums.
 #include "plx_internal.h"
 
 #include <algorithm>
-#include <initializer_list>
 
 namespace plx {
 
@@ -23,8 +23,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kGram64Blocks = 512;    // most workgroups of the gram kernel = partial sums per (j, c); the work buffer is sized for it
 constexpr int kPcg64Cols = 16;        // column tile: the N of the 16x16x4 MFMA; G and T are [kp][16]
-constexpr int kFinal64Block = 1024;
-constexpr double kTiny64 = 1e-300;
 
 // ---- G = L^T R ---------------------------------------------------------------------------------------------------
 // pcg_gram_kernel's tile walk: one wave per 64-row tile, lane l loads the 16 bytes lt[j][i0 + 16 s + 4 (l >> 4) .. + 3]
@@ -216,98 +214,6 @@ __global__ __launch_bounds__(kBlock) void pcg64_apply_kernel(const float *__rest
     }
 }
 
-// One workgroup per column over `nrows` partial rows of `stride` doubles (the scheme of plx_cg_f64.hip's final stage):
-// thread-strided sums (four loads in flight), then a tree.
-__global__ __launch_bounds__(kFinal64Block) void pcg64_rz_final_kernel(const double *__restrict__ partial, int nrows,
-                                                                       int stride, double *__restrict__ out)
-{
-    __shared__ double red[kFinal64Block];
-    const int c = blockIdx.x;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    int k = threadIdx.x;
-    for (; k + 3 * kFinal64Block < nrows; k += 4 * kFinal64Block) {
-        const double p0 = partial[(size_t)k * stride + c], p1 = partial[(size_t)(k + kFinal64Block) * stride + c];
-        const double p2 = partial[(size_t)(k + 2 * kFinal64Block) * stride + c];
-        const double p3 = partial[(size_t)(k + 3 * kFinal64Block) * stride + c];
-        a0 += p0; a1 += p1; a2 += p2; a3 += p3;
-    }
-    for (; k < nrows; k += kFinal64Block) a0 += partial[(size_t)k * stride + c];
-    red[threadIdx.x] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    for (int s = kFinal64Block / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[c] = red[0];
-}
-
-// ---- direction of a preconditioned iteration: cg64_step_direction_kernel with Z as the source and the true residual
-// |R|^2 in the activity test -----------------------------------------------------------------------------------------------
-__device__ __forceinline__ double pcg64_beta(const double *rz_new, const double *rz, const double *active, int c)
-{
-    return active[c] > 0.0 ? rz_new[c] / fmax(rz[c], kTiny64) : 0.0;
-}
-
-__device__ __forceinline__ void pcg64_direction_scalars(const double *rz_new, const double *rz, const double *rr,
-                                                        const double *active, const double *b_norm, double tol, int vd,
-                                                        double *beta_out, double *active_out)
-{
-    if (blockIdx.x == 0 && (int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        beta_out[c] = pcg64_beta(rz_new, rz, active, c);
-        active_out[c] = (active[c] > 0.0 && sqrt(rr[c]) / b_norm[c] > tol) ? 1.0 : 0.0;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void pcg64_step_direction_kernel(double *__restrict__ P, const double *__restrict__ Z,
-                                                                      const double *__restrict__ rz_new,
-                                                                      const double *__restrict__ rz,
-                                                                      const double *__restrict__ rr,
-                                                                      const double *__restrict__ active,
-                                                                      const double *__restrict__ b_norm, double tol,
-                                                                      int64_t total, int vd, double *__restrict__ beta_out,
-                                                                      double *__restrict__ active_out)
-{
-    __shared__ double sbeta[kBlock];
-    if ((int)threadIdx.x < vd) sbeta[threadIdx.x] = pcg64_beta(rz_new, rz, active, threadIdx.x);
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < total) {
-        const uint32_t uvd = (uint32_t)vd;
-        const uint32_t bm = ((blockIdx.x % uvd) * ((uint32_t)kBlock % uvd)) % uvd;      // wave-uniform
-        const uint32_t c = (bm + threadIdx.x) % uvd;
-        P[i] = Z[i] + P[i] * sbeta[c];
-    }
-    pcg64_direction_scalars(rz_new, rz, rr, active, b_norm, tol, vd, beta_out, active_out);
-}
-
-// the same two elements per thread (16-byte loads / stores; total even, P and Z 16-byte aligned)
-__global__ __launch_bounds__(kBlock) void pcg64_step_direction2_kernel(double2 *__restrict__ P, const double2 *__restrict__ Z,
-                                                                       const double *__restrict__ rz_new,
-                                                                       const double *__restrict__ rz,
-                                                                       const double *__restrict__ rr,
-                                                                       const double *__restrict__ active,
-                                                                       const double *__restrict__ b_norm, double tol,
-                                                                       int64_t pairs, int vd, double *__restrict__ beta_out,
-                                                                       double *__restrict__ active_out)
-{
-    __shared__ double sbeta[kBlock];
-    if ((int)threadIdx.x < vd) sbeta[threadIdx.x] = pcg64_beta(rz_new, rz, active, threadIdx.x);
-    __syncthreads();
-    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q < pairs) {
-        const uint32_t uvd = (uint32_t)vd;
-        const uint32_t bm = ((blockIdx.x % uvd) * ((2u * (uint32_t)kBlock) % uvd)) % uvd;      // wave-uniform
-        uint32_t c = (bm + 2u * threadIdx.x) % uvd;
-        const double2 z = Z[q];
-        double2 p = P[q];
-        p.x = z.x + p.x * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
-        p.y = z.y + p.y * sbeta[c];
-        P[q] = p;
-    }
-    pcg64_direction_scalars(rz_new, rz, rr, active, b_norm, tol, vd, beta_out, active_out);
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------
 // workgroups of the gram kernel = partial rows the final sum walks: one per four tiles (a wave each) up to kGram64Blocks
 static int gram64_parts(int64_t n) { return (int)std::min<int64_t>(kGram64Blocks, ceil_div(ceil_div(n, 64), kBlock / 64)); }
@@ -359,13 +265,7 @@ static int check_pcg64(const char *who, const void *lt, int64_t ld, int kp, int6
         return PLX_ERR_INVALID;
     }
     if ((reinterpret_cast<uintptr_t>(lt) & 15) != 0) { set_error("%s: the factor must be 16-byte aligned", who); return PLX_ERR_INVALID; }
-    uintptr_t bits = 0;
-    for (const void *q : ptrs) {
-        if (!q) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
-        bits |= (uintptr_t)q;
-    }
-    if ((bits & 7) != 0) { set_error("%s: buffers of doubles must be 8-byte aligned", who); return PLX_ERR_INVALID; }
-    return PLX_OK;
+    return check_cg64(who, ptrs, n, t);          // (n and t are inside its ranges by now: the pointer checks remain)
 }
 
 }  // namespace plx
@@ -415,10 +315,7 @@ extern "C" int plx_pcg_apply_f64(const float *d_lt, int64_t ld, int kp, int k, c
     const bool vec = ((reinterpret_cast<uintptr_t>(d_r) | reinterpret_cast<uintptr_t>(d_z)) & 15) == 0;
     if (vec) PLX_TRY(apply64_launch<true>(d_lt, ld, k, d_r, n, t, d_t, d_scale, d_z, part, s));
     else PLX_TRY(apply64_launch<false>(d_lt, ld, k, d_r, n, t, d_t, d_scale, d_z, part, s));
-    if (d_rz) {
-        pcg64_rz_final_kernel<<<t, kFinal64Block, 0, s>>>(part, ceil_div(n, kBlock), t, d_rz);
-        PLX_HIP_TRY(hipGetLastError());
-    }
+    if (d_rz) PLX_TRY(coldot_final_f64(part, ceil_div(n, kBlock), t, t, d_rz, s));
     return PLX_OK;
 }
 
@@ -426,28 +323,6 @@ extern "C" int plx_pcg_step_direction_f64(double *d_p, const double *d_z, const 
                                           const double *d_rr, const double *d_active, const double *d_b_norm, double tol,
                                           int64_t n, int vd, double *d_beta, double *d_active_out, void *stream)
 {
-    const char *who = "plx_pcg_step_direction_f64";
-    uintptr_t bits = 0;
-    for (const void *q : {(const void *)d_p, (const void *)d_z, (const void *)d_rz_new, (const void *)d_rz, (const void *)d_rr,
-                          (const void *)d_active, (const void *)d_b_norm, (const void *)d_beta, (const void *)d_active_out}) {
-        if (!q) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
-        bits |= (uintptr_t)q;
-    }
-    if (vd < 1 || vd > kBlock) { set_error("%s: vd = %d outside 1..%d", who, vd, kBlock); return PLX_ERR_INVALID; }
-    if (n < 1) { set_error("%s: n = %lld must be positive", who, (long long)n); return PLX_ERR_INVALID; }
-    if ((bits & 7) != 0) { set_error("%s: buffers of doubles must be 8-byte aligned", who); return PLX_ERR_INVALID; }
-    if (d_active == d_active_out) { set_error("%s: active and active_out must be different buffers", who); return PLX_ERR_INVALID; }
-    const int64_t total = n * vd;
-    hipStream_t s = (hipStream_t)stream;
-    if ((total & 1) == 0 && ((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_z)) & 15) == 0) {
-        const int64_t pairs = total / 2;
-        pcg64_step_direction2_kernel<<<ceil_div(pairs, kBlock), kBlock, 0, s>>>(
-            reinterpret_cast<double2 *>(d_p), reinterpret_cast<const double2 *>(d_z), d_rz_new, d_rz, d_rr, d_active, d_b_norm,
-            tol, pairs, vd, d_beta, d_active_out);
-    } else {
-        pcg64_step_direction_kernel<<<ceil_div(total, kBlock), kBlock, 0, s>>>(d_p, d_z, d_rz_new, d_rz, d_rr, d_active, d_b_norm,
-                                                                              tol, total, vd, d_beta, d_active_out);
-    }
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
+    return step_direction_f64("plx_pcg_step_direction_f64", d_p, d_z, d_rz_new, d_rz, d_rr, d_active, d_b_norm, tol, n, vd,
+                              d_beta, d_active_out, (hipStream_t)stream);
 }

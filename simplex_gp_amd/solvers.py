@@ -74,6 +74,16 @@ def _coldot_work(device, t, dtype):
     return work
 
 
+def _fused_work(device, t):
+    """The work buffer of the fused fp32 step forms (plx_cg_step_*_fused) for t columns, per device."""
+    from . import _native as nv
+    key = (device.index, t, "fused")
+    work = _dot_work.get(key)
+    if work is None:
+        work = _dot_work[key] = torch.empty(int(nv.lib().plx_cg_fused_work_floats(t)), dtype=torch.float32, device=device)
+    return work
+
+
 def _native_ok(*ts, f64_ok=False):
     """All tensors contiguous 2-D CUDA matrices of one shape, at most 256 columns, all float32 -- or, with f64_ok (the
     calls that have a double form), all float64 while NATIVE_CG_F64 is on."""
@@ -88,11 +98,7 @@ def _cg_update(X, R, P, AP, alpha, reduce=None):
         import ctypes
         from . import _native as nv
         n, t = X.shape
-        key = (X.device.index, t)
-        work = _dot_work.get(key)
-        if work is None:
-            work = _dot_work[key] = torch.empty(int(nv.lib().plx_coldot_work_floats(t)), dtype=torch.float32,
-                                                device=X.device)
+        work = _coldot_work(X.device, t, torch.float32)
         out = torch.empty(t, dtype=torch.float32, device=X.device)
         alpha = alpha.to(torch.float32).contiguous()
         p = lambda a: ctypes.c_void_p(a.data_ptr())          # noqa: E731
@@ -628,107 +634,57 @@ def _stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _batched_pcg_native_f64(matmul, B, precond, max_iter, tol, want_tridiag, check_every, matmul_dot=None, floor=0):
-    """_batched_pcg_native in double, rows in the caller's order, without the fused step forms: per iteration one MVM
-    (with its p^T A p where the product serves it), plx_cg_step_update_f64 (alpha = rz / pAp, X, R, |R|^2), the
-    preconditioner (plx_pcg_project_f64 + plx_pcg_apply_f64: Z = P^-1 R and <R, Z>) and plx_pcg_step_direction_f64."""
-    from . import _native as nv
-    lib = nv.lib()
-    n, t = B.shape
-    dev = B.device
-    X = torch.zeros_like(B)
-    R = B.clone().contiguous()
-    rz = torch.empty(t, dtype=torch.float64, device=dev)
-    rz_new = torch.empty_like(rz)
-    Z = precond.solve_rows(R, rz=rz)
-    P = Z.clone()
-    rz0 = rz.clone()
-    rr = _colsum(R, R)
-    b_norm = rr.sqrt().clamp_min(1e-300)
-    rr = rr.clone()
-    active = torch.ones(t, dtype=torch.float64, device=dev)
-    active_next = torch.empty_like(active)
-    work = _coldot_work(dev, t, torch.float64)
-    alphas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=torch.float64, device=dev)
-    betas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=torch.float64, device=dev)
-    it = 0
-    with torch.cuda.device(dev):
-        stream = _stream(dev)
-        for it in range(1, max_iter + 1):
-            if matmul_dot is not None:
-                AP, pAp = matmul_dot(P)
-                pAp = pAp.contiguous()
-            else:
-                AP = matmul(P)
-                AP = AP if AP.is_contiguous() else AP.contiguous()
-                pAp = _colsum(P, AP)
-            row = it - 1 if want_tridiag else 0
-            nv.check(lib.plx_cg_step_update_f64(_vp(X), _vp(R), _vp(P), _vp(AP), _vp(rz), _vp(pAp), _vp(active), n, t, _vp(rr),
-                                                _vp(alphas[row]), _vp(work), stream), "plx_cg_step_update_f64")
-            precond.solve_rows(R, out=Z, rz=rz_new)
-            step_tol = float(tol) if it >= floor else min(float(tol), _FROZEN_BELOW)
-            nv.check(lib.plx_pcg_step_direction_f64(_vp(P), _vp(Z), _vp(rz_new), _vp(rz), _vp(rr), _vp(active), _vp(b_norm),
-                                                    step_tol, n, t, _vp(betas[row]), _vp(active_next), stream),
-                     "plx_pcg_step_direction_f64")
-            rz, rz_new = rz_new, rz
-            active, active_next = active_next, active
-            if tol > 0 and (it % check_every == 0 or it == max_iter) and not bool(active.any()):
-                break
-    info = {"iterations": it, "residual": (rr.sqrt() / b_norm), "rz0": rz0}
-    if want_tridiag:
-        info["tridiag"] = _tridiag_from_cg(alphas[:it], betas[:it], B, info)
-    return X, info
-
-
 def _batched_pcg_native(matmul, B, precond, max_iter, tol, want_tridiag, check_every, matmul_dot=None, floor=0):
-    """Preconditioned batched CG on one GPU, rows in lattice order, scalars on the device: per iteration one MVM (with
-    its p^T A p), plx_cg_step_update (alpha = rz / pAp, X, R, |R|^2), the preconditioner (plx_pcg_project +
-    plx_pcg_apply: Z = P^-1 R and <R, Z>) and plx_pcg_step_direction (beta = rz' / rz, P = Z + beta P, active)."""
-    import ctypes
+    """Preconditioned batched CG on one GPU, rows in the order the preconditioner's native solve takes, scalars on the
+    device: per iteration one MVM (with its p^T A p where the product serves it), plx_cg_step_update[_f64] (alpha = rz / pAp,
+    X, R, |R|^2), the preconditioner (project + apply: Z = P^-1 R and <R, Z>) and plx_pcg_step_direction[_f64] (beta =
+    rz' / rz, P = Z + beta P, active).  fp32: LatticePreconditioner.solve_lattice, rows in lattice order; float64:
+    LatticePreconditioner64.solve_rows, rows in the caller's order, every small array in the dtype of B (no fused step
+    forms in double)."""
     from . import _native as nv
     lib = nv.lib()
     n, t = B.shape
     dev = B.device
+    f64 = B.dtype == torch.float64
+    step_update, step_update_name = (lib.plx_cg_step_update_f64, "plx_cg_step_update_f64") if f64 \
+        else (lib.plx_cg_step_update, "plx_cg_step_update")
+    step_direction, step_direction_name = (lib.plx_pcg_step_direction_f64, "plx_pcg_step_direction_f64") if f64 \
+        else (lib.plx_pcg_step_direction, "plx_pcg_step_direction")
+    solve = precond.solve_rows if f64 else precond.solve_lattice
     X = torch.zeros_like(B)
     R = B.clone().contiguous()
-    rz = torch.empty(t, dtype=torch.float32, device=dev)
+    rz = torch.empty(t, dtype=B.dtype, device=dev)
     rz_new = torch.empty_like(rz)
-    Z = precond.solve_lattice(R, rz=rz)
+    Z = solve(R, rz=rz)
     P = Z.clone()
     rz0 = rz.clone()
     rr = _colsum(R, R)
-    b_norm = rr.sqrt().clamp_min(1e-30)
+    b_norm = rr.sqrt().clamp_min(1e-300 if f64 else 1e-30)
     rr = rr.clone()
-    active = torch.ones(t, dtype=torch.float32, device=dev)
+    active = torch.ones(t, dtype=B.dtype, device=dev)
     active_next = torch.empty_like(active)
-    key = (dev.index, t)
-    work = _dot_work.get(key)
-    if work is None:
-        work = _dot_work[key] = torch.empty(int(lib.plx_coldot_work_floats(t)), dtype=torch.float32, device=dev)
-    alphas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=torch.float32, device=dev)
-    betas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=torch.float32, device=dev)
+    work = _coldot_work(dev, t, B.dtype)
+    alphas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=B.dtype, device=dev)
+    betas = torch.zeros(max_iter if want_tridiag else 1, t, dtype=B.dtype, device=dev)
     it = 0
     # the iteration without its three stand-alone reductions (pAp, |R|^2, <R, Z>): the partial sums are added up inside the
     # update and the direction kernels (plx_cg_step_update_fused, plx_pcg_step_direction_fused)
-    partial_mm = getattr(matmul_dot, "partial", None) if _fuse_cg_steps(n) else None
+    partial_mm = getattr(matmul_dot, "partial", None) if _fuse_cg_steps(n) and not f64 else None
     fused = partial_mm is not None and int(lib.plx_cg_fused_work_floats(t)) > 0
     if fused:
-        fkey = (dev.index, t, "fused")
-        fwork = _dot_work.get(fkey)
-        if fwork is None:
-            fwork = _dot_work[fkey] = torch.empty(int(lib.plx_cg_fused_work_floats(t)), dtype=torch.float32, device=dev)
+        fwork = _fused_work(dev, t)
         pwork = precond._workspace(t)
         rz_part = pwork[int(lib.plx_pcg_rz_partial_offset(precond.kp)):]
         nrz = int(lib.plx_pcg_rz_partial_rows(n, precond.factor_type))
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _stream(dev)
         for it in range(1, max_iter + 1):
             if fused:
                 AP, pap_part, tiles = partial_mm(P)
                 row = it - 1 if want_tridiag else 0
                 nv.check(lib.plx_cg_step_update_fused(_vp(X), _vp(R), _vp(P), _vp(AP), _vp(rz), _vp(pap_part), tiles, _vp(active), n, t,
                                                       _vp(alphas[row]), _vp(fwork), stream), "plx_cg_step_update_fused")
-                precond.solve_lattice(R, out=Z, rz=None)              # <R, Z> stays as partial sums in the preconditioner's work buffer
+                solve(R, out=Z, rz=None)              # <R, Z> stays as partial sums in the preconditioner's work buffer
                 step_tol = float(tol) if it >= floor else min(float(tol), _FROZEN_BELOW)
                 nv.check(lib.plx_pcg_step_direction_fused(_vp(P), _vp(Z), _vp(rz_part), nrz, _vp(fwork), _vp(rz), _vp(active), _vp(b_norm),
                                                           step_tol, n, t, _vp(rz_new), _vp(rr), _vp(betas[row]), _vp(active_next),
@@ -746,12 +702,12 @@ def _batched_pcg_native(matmul, B, precond, max_iter, tol, want_tridiag, check_e
                 AP = AP if AP.is_contiguous() else AP.contiguous()
                 pAp = _colsum(P, AP)
             row = it - 1 if want_tridiag else 0
-            nv.check(lib.plx_cg_step_update(_vp(X), _vp(R), _vp(P), _vp(AP), _vp(rz), _vp(pAp), _vp(active), n, t, _vp(rr),
-                                            _vp(alphas[row]), _vp(work), stream), "plx_cg_step_update")
-            precond.solve_lattice(R, out=Z, rz=rz_new)
+            nv.check(step_update(_vp(X), _vp(R), _vp(P), _vp(AP), _vp(rz), _vp(pAp), _vp(active), n, t, _vp(rr),
+                                 _vp(alphas[row]), _vp(work), stream), step_update_name)
+            solve(R, out=Z, rz=rz_new)
             step_tol = float(tol) if it >= floor else min(float(tol), _FROZEN_BELOW)
-            nv.check(lib.plx_pcg_step_direction(_vp(P), _vp(Z), _vp(rz_new), _vp(rz), _vp(rr), _vp(active), _vp(b_norm), step_tol,
-                                                n, t, _vp(betas[row]), _vp(active_next), stream), "plx_pcg_step_direction")
+            nv.check(step_direction(_vp(P), _vp(Z), _vp(rz_new), _vp(rz), _vp(rr), _vp(active), _vp(b_norm), step_tol,
+                                    n, t, _vp(betas[row]), _vp(active_next), stream), step_direction_name)
             rz, rz_new = rz_new, rz
             active, active_next = active_next, active
             if tol > 0 and (it % check_every == 0 or it == max_iter) and not bool(active.any()):
@@ -777,7 +733,7 @@ def _iteration_floor(max_iter, want_tridiag, min_iter, min_tridiag_iter):
 
 
 def batched_cg(matmul, B, max_iter=1000, tol=1e-4, reduce=None, want_tridiag=False, check_every=4, precond=None,
-               matmul_dot=None, min_iter=10, min_tridiag_iter=20, lattice_rows=False):
+               matmul_dot=None, min_iter=10, min_tridiag_iter=20, native_precond=False):
     """Solve A X = B for all columns of B at once (A symmetric positive definite,
     known through `matmul`).  Stops when every column's residual norm is below
     `tol` x its right-hand-side norm, or after max_iter iterations.  The stopping
@@ -796,19 +752,25 @@ def batched_cg(matmul, B, max_iter=1000, tol=1e-4, reduce=None, want_tridiag=Fal
     `min_iter` / `min_tridiag_iter`: iteration floor as in GPyTorch's linear_cg (see _iteration_floor); before it only
     columns that have converged to rounding level (relative residual < 1e-10) are frozen.
 
-    `lattice_rows`: the rows of B (and what `matmul` takes and returns) are in the row order of precond.lat, a
-    LatticePreconditioner -- the native preconditioned iteration runs; any other combination goes through
-    precond.solve(), which takes rows in the caller's order.
+    `native_precond`: the rows of B (and what `matmul` takes and returns) are in the order the preconditioner's native
+    solve takes -- lattice order for a LatticePreconditioner (fp32 B), the caller's order for a LatticePreconditioner64
+    (float64 B, while NATIVE_PCG_F64 is on) -- and the native preconditioned iteration runs; without it a preconditioner
+    goes through precond.solve(), which takes rows in the caller's order.
 
     Returns (X, info); with want_tridiag, info["tridiag"] holds the per-column
     Lanczos tridiagonals rebuilt from the CG coefficients (mBCG), shape [t, k, k].
     """
     floor = _iteration_floor(max_iter, want_tridiag, min_iter, min_tridiag_iter)
-    if lattice_rows:
-        # only the native iteration works in the preconditioner's row order: precond.solve() takes caller-order rows, and
-        # a silently permuted P^-1 is a different preconditioner from the one behind the probes and logdet(P)
-        if not (isinstance(precond, LatticePreconditioner) and reduce is None and _native_ok(B) and B.shape[1] <= 16):
-            raise ValueError("batched_cg(lattice_rows=True) needs a LatticePreconditioner, reduce=None and a contiguous fp32 "
+    if native_precond:
+        # only the native iteration works in the preconditioner's own row order: precond.solve() takes caller-order rows,
+        # and a silently permuted P^-1 is a different preconditioner from the one behind the probes and logdet(P)
+        if isinstance(precond, LatticePreconditioner64):
+            pair = B.dtype == torch.float64 and NATIVE_PCG_F64
+        else:
+            pair = isinstance(precond, LatticePreconditioner) and B.dtype == torch.float32
+        if not (pair and reduce is None and B.is_cuda and B.dim() == 2 and B.is_contiguous() and B.shape[1] <= 16):
+            raise ValueError("batched_cg(native_precond=True) needs a LatticePreconditioner with an fp32 right-hand side or a "
+                             "LatticePreconditioner64 with a float64 one (NATIVE_PCG_F64 on), reduce=None and a contiguous "
                              "CUDA right-hand side of at most 16 columns (got %s, reduce=%s, B %s %s)"
                              % (type(precond).__name__, "set" if reduce is not None else None, tuple(B.shape), B.dtype))
         return _batched_pcg_native(matmul, B, precond, max_iter, tol, want_tridiag, check_every, matmul_dot, floor)
@@ -894,10 +856,7 @@ def _batched_cg_native(matmul, B, max_iter, tol, want_tridiag, check_every, matm
     partial_mm = getattr(matmul_dot, "partial", None) if _fuse_cg_steps(n) and not f64 else None
     fused = partial_mm is not None and int(lib.plx_cg_fused_work_floats(t)) > 0
     if fused:
-        fkey = (dev.index, t, "fused")
-        fwork = _dot_work.get(fkey)
-        if fwork is None:
-            fwork = _dot_work[fkey] = torch.empty(int(lib.plx_cg_fused_work_floats(t)), dtype=torch.float32, device=dev)
+        fwork = _fused_work(dev, t)
     with torch.cuda.device(dev):
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for it in range(1, max_iter + 1):
@@ -1207,7 +1166,7 @@ class LatticeGP(nn.Module):
                     def fused_dot(V):
                         return lat.apply_affine(V, ss, want_dot=True)
                     fused_dot.partial = lambda V: lat.apply_affine(V, ss, want_dot="partial")
-                sol, info = batched_cg(lambda V: lat.apply_affine(V, ss), rhs_l, matmul_dot=fused_dot, lattice_rows=native_pre,
+                sol, info = batched_cg(lambda V: lat.apply_affine(V, ss), rhs_l, matmul_dot=fused_dot, native_precond=native_pre,
                                        **cg_args)
                 if pad:
                     sol = sol[:, :t].contiguous()
@@ -1240,17 +1199,9 @@ class LatticeGP(nn.Module):
         if lat.affine_dot_f64_ok(rhs.shape[1]):
             def fused_dot(V):
                 return lat.apply_affine(V, ss, want_dot=True)
-        if native_pre:
-            # the preconditioner's rows are in the caller's order like the product's: the native double iteration
-            # (batched_cg's arguments and defaults, bound through its own signature)
-            import inspect
-            a = inspect.signature(batched_cg).bind(None, rhs, **cg_args)
-            a.apply_defaults()
-            a = a.arguments
-            floor = _iteration_floor(a["max_iter"], a["want_tridiag"], a["min_iter"], a["min_tridiag_iter"])
-            return _batched_pcg_native_f64(lambda V: lat.apply_affine(V.contiguous(), ss), rhs, pre, a["max_iter"], a["tol"],
-                                           a["want_tridiag"], a["check_every"], fused_dot, floor)
-        return batched_cg(lambda V: lat.apply_affine(V.contiguous(), ss), rhs, matmul_dot=fused_dot, **cg_args)
+        # (a native preconditioner's rows are in the caller's order like the product's)
+        return batched_cg(lambda V: lat.apply_affine(V.contiguous(), ss), rhs, matmul_dot=fused_dot, native_precond=native_pre,
+                          **cg_args)
 
     def preconditioner(self, x, rank, K=None, factor_dtype=torch.float16):
         """Rank-`rank` pivoted-Cholesky preconditioner of (s K + sigma^2 I) (no gradients).  On the HIP path it is

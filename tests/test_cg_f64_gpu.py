@@ -67,7 +67,7 @@ def axpy_ld(y, a, x):
 
 def direction_kernel(n, vd, off):
     """plx_cg_step_direction_f64: two elements per thread when n vd is even and both matrices are 16-byte aligned."""
-    return "cg64_step_direction2_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "cg64_step_direction_kernel"
+    return "step_direction64_pair_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "step_direction64_kernel"
 
 
 def work_doubles(vd):
@@ -493,6 +493,6 @@ def test_every_new_kernel_was_launched():
         literals.update(re.findall(r'"([^"]*)"', stmt.group(1)))
     assert literals == {AFF_V1, AFF_CHUNK, AFF_WIDE}, literals
     assert kernels == {"coldot64_partial_kernel", "coldot64_final_kernel", "cg64_step_update_kernel",
-                       "cg64_step_direction_kernel", "cg64_step_direction2_kernel", AFF_V1, AFF_CHUNK, AFF_WIDE}, kernels
+                       "step_direction64_kernel", "step_direction64_pair_kernel", AFF_V1, AFF_CHUNK, AFF_WIDE}, kernels
     assert kernels <= REACHED, sorted(kernels - REACHED)
     assert all(v <= 1.0 for v in WORST.values()), WORST

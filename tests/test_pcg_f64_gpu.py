@@ -76,7 +76,7 @@ def factor(rng, n, k, kp):
 
 
 def direction_kernel(n, vd, off):
-    return "pcg64_step_direction2_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "pcg64_step_direction_kernel"
+    return "step_direction64_pair_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "step_direction64_kernel"
 
 
 def bits(t):
@@ -162,7 +162,7 @@ def test_pcg64_kernels(n, k, kp):
             assert e <= (k + 6) * U2, (label, "apply", e)
             prod = ld_(r) * ld_(z)
             e = entry_ratio(rz, f64_(prod.sum(0)), f64_(np.abs(prod).sum(0)))
-            note("pcg64_rz_final_kernel", e, (n + 4) * U2)
+            note("coldot64_final_kernel", e, (n + 4) * U2)
             assert e <= (n + 4) * U2, (label, "rz", e)
             # rz = NULL: the same Z
             Z2 = Buf(count=n * t, offset=off, dtype=F64)
@@ -202,6 +202,74 @@ def test_pcg64_kernels(n, k, kp):
             if inactive is not None:
                 assert gb[inactive] == 0.0 and gact[inactive] == 0.0
                 assert np.array_equal(gp[:, inactive].view(np.int64), z[:, inactive].view(np.int64)), (label, "P = Z of a frozen column")
+
+
+def test_apply_large_reaches_the_unrolled_final_sum():
+    """n = 786,689 at kp = 16, k = 1, t = 2: <R, Z> has 3074 partial rows (one per 256 rows), more than 3 * 1024, so
+    coldot64_final_kernel's four-way unrolled loop runs -- plx_coldot_f64 always hands it 1024 rows.  The <R, Z> bar of
+    test_pcg64_kernels, (n + 4) U2 on the entry ratio against longdouble from the device's own Z."""
+    lib = nv.lib()
+    n, k, kp, t = 786_689, 1, 16, 2
+    assert (n + 255) // 256 == 3074
+    rng = np.random.default_rng(n)
+    lt, ld = factor(rng, n, k, kp)
+    assert ld == 786_752
+    LT = Buf(lt, dtype=F32)
+    r, tm = rng.standard_normal((n, t)), rng.standard_normal((kp, 16))
+    scale = np.array([1.25, -0.375])
+    R, TM, SC = Buf(r, dtype=F64), Buf(tm, dtype=F64), Buf(scale, dtype=F64)
+    work = Buf(count=work_doubles(n, kp, t), dtype=F64)
+    Z, RZ = Buf(count=n * t, dtype=F64), Buf(count=t, dtype=F64)
+    nv.check(lib.plx_pcg_apply_f64(LT.ptr, ld, kp, k, R.ptr, n, t, TM.ptr, SC.ptr, Z.ptr, RZ.ptr, work.ptr, stream()),
+             "plx_pcg_apply_f64")
+    check_buffers(inputs=(LT, R, TM, SC), outputs=(Z, RZ, work))
+    z, rz = Z.np(n, t), RZ.np()
+    lcol, tk = ld_(lt[:k, :n]).T, ld_(tm[:k, :t])
+    z_want = f64_((scale[0] * ld_(r) - lcol @ tk) * scale[1])
+    Tz = f64_((np.abs(scale[0] * ld_(r)) + np.abs(lcol) @ np.abs(tk)) * abs(scale[1]))
+    e = entry_ratio(z, z_want, Tz)
+    note(f"pcg64_apply_kernel<{t}>", e, (k + 6) * U2)
+    assert e <= (k + 6) * U2, ("apply", e)
+    prod = ld_(r) * ld_(z)
+    e = entry_ratio(rz, f64_(prod.sum(0)), f64_(np.abs(prod).sum(0)))
+    note("coldot64_final_kernel", e, (n + 4) * U2)
+    print(f"<R, Z> over 3074 partial rows: error / ((n + 4) U2) = {e / ((n + 4) * U2):.4f}")
+    assert e <= (n + 4) * U2, ("rz", e)
+
+
+@pytest.mark.parametrize("vd", (3, 12))
+@pytest.mark.parametrize("n", (1, 257))
+def test_cg_direction_is_the_pcg_direction(n, vd):
+    """plx_cg_step_direction_f64(P, R, rs_new, rs, ...) is plx_pcg_step_direction_f64(P, R, rs_new, rs, rr = rs_new, ...):
+    P, beta and active_out agree bit for bit, buffers aligned and offset by one double (the scalar and the pair form each
+    way), one column inactive and the columns on either side of tol."""
+    lib = nv.lib()
+    rng = np.random.default_rng(10 * n + vd)
+    p0, r0 = rng.standard_normal((n, vd)), rng.standard_normal((n, vd))
+    rs_new, rs = rng.uniform(0.5, 2.0, vd) * n, rng.uniform(0.5, 2.0, vd) * n
+    tol = 1e-3
+    b_norm = np.sqrt(rs_new) / tol * np.where(np.arange(vd) % 2 == 0, 0.5, 2.0)
+    act = np.ones(vd)
+    act[vd // 2] = 0.0
+    for off in (0, 1):
+        RSN, RS, ACT, BN = (Buf(a, dtype=F64) for a in (rs_new, rs, act, b_norm))
+        outs = []
+        for pcg in (False, True):
+            P, R = Buf(p0, offset=off, dtype=F64), Buf(r0, offset=off, dtype=F64)
+            beta, act_out = Buf(count=vd, offset=off, dtype=F64), Buf(count=vd, offset=off, dtype=F64)
+            if pcg:
+                nv.check(lib.plx_pcg_step_direction_f64(P.ptr, R.ptr, RSN.ptr, RS.ptr, RSN.ptr, ACT.ptr, BN.ptr, tol, n, vd,
+                                                        beta.ptr, act_out.ptr, stream()), "plx_pcg_step_direction_f64")
+            else:
+                nv.check(lib.plx_cg_step_direction_f64(P.ptr, R.ptr, RSN.ptr, RS.ptr, ACT.ptr, BN.ptr, tol, n, vd, beta.ptr,
+                                                       act_out.ptr, stream()), "plx_cg_step_direction_f64")
+            check_buffers(inputs=(R, RSN, RS, ACT, BN), outputs=(P, beta, act_out))
+            outs.append((P.cpu(), beta.cpu(), act_out.cpu()))
+        for name, u, v in zip(("P", "beta", "active_out"), *outs):
+            assert torch.equal(bits(u), bits(v)), (n, vd, off, name)
+        REACHED.add(direction_kernel(n, vd, off))
+        gp, gb, gact = (x.numpy() for x in outs[0])
+        assert not np.array_equal(gp, p0.reshape(-1)) and set(gact.tolist()) == {0.0, 1.0} and gb[vd // 2] == 0.0
 
 
 @pytest.mark.parametrize("vd", (3, 12))
@@ -439,15 +507,15 @@ def test_khat_solve_preconditioned():
         its = {}
         for native in (True, False):
             called = []
-            real = solvers._batched_pcg_native_f64
-            solvers._batched_pcg_native_f64 = lambda *a, **k: (called.append(1), real(*a, **k))[1]
+            real = solvers._batched_pcg_native
+            solvers._batched_pcg_native = lambda *a, **k: (called.append(1), real(*a, **k))[1]
             solvers.NATIVE_PCG_F64 = native
             try:
                 X, info = model.khat_solve(xt, rhs, tol=1e-11, max_iter=1000, precond=pre, check_every=check_every,
                                            want_tridiag=True)
             finally:
                 solvers.NATIVE_PCG_F64 = True
-                solvers._batched_pcg_native_f64 = real
+                solvers._batched_pcg_native = real
             assert bool(called) == native
             assert X.dtype == F64 and X.shape == rhs.shape and info["rz0"].dtype == F64
             assert tuple(info["tridiag"].shape) == (3, info["iterations"], info["iterations"])
@@ -557,16 +625,17 @@ def report():
 
 
 def test_every_new_kernel_was_launched():
-    """Every __global__ kernel of plx_pcg_f64.hip and every column count of the apply pass ran in this module (run as a
-    whole), under its bar."""
+    """Every __global__ kernel of plx_pcg_f64.hip, every column count of the apply pass and the three kernels of
+    plx_cg_f64.hip that this file's entry points launch (the final sum of <R, Z>, the two direction forms) ran in this module
+    (run as a whole), under its bar."""
     print(report())
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     text = open(os.path.join(root, "simplex_gp_amd", "csrc", "plx_pcg_f64.hip")).read()
     text = re.sub(r"//[^\n]*", "", text)
     kernels = set(re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s*)?void\s+(\w+)\s*\(", text))
-    assert kernels == {"pcg64_gram_kernel", "pcg64_project_kernel", "pcg64_apply_kernel", "pcg64_rz_final_kernel",
-                       "pcg64_step_direction_kernel", "pcg64_step_direction2_kernel"}, kernels
+    assert kernels == {"pcg64_gram_kernel", "pcg64_project_kernel", "pcg64_apply_kernel"}, kernels
+    shared = {"coldot64_final_kernel", "step_direction64_kernel", "step_direction64_pair_kernel"}
     reached = {k.split("<")[0] for k in REACHED}
-    assert kernels <= reached, sorted(kernels - reached)
+    assert kernels | shared <= reached, sorted((kernels | shared) - reached)
     assert {f"pcg64_apply_kernel<{t}>" for t in TS} <= REACHED
     assert all(v <= 1.0 for v in WORST.values()), WORST

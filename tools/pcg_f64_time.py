@@ -11,7 +11,7 @@ Per shape, rank 100, 11 columns of doubles:
                  native: LatticePreconditioner64.solve_rows (plx_pcg_project_f64 + plx_pcg_apply_f64)
                  parent: PivotedCholeskyPreconditioner(dtype=float64).solve (two GEMMs and a cholesky_solve)
     iteration  one preconditioned CG iteration
-                 native: the body of solvers._batched_pcg_native_f64 (plx_apply_affine_f64 with its dot,
+                 native: the float64 body of solvers._batched_pcg_native (plx_apply_affine_f64 with its dot,
                          plx_cg_step_update_f64, the two passes, plx_pcg_step_direction_f64)
                  parent: the body of solvers._batched_pcg on lat.apply(V).mul_(s).addcmul_(V, noise)
     build      the factor and C
