@@ -578,6 +578,29 @@ int plx_exact_mvm(const float *d_x1, int64_t n1, const float *d_x2, int64_t n2, 
 int plx_exact_grad(const float *d_x1, int64_t n1, const float *d_x2, int64_t n2, int d, int profile,
                    const float *d_g, const float *d_v, int t, float *d_grad_x1, void *d_work, int64_t work_bytes,
                    void *stream);
+/*
+ * The same two products with every array in double (csrc/plx_exact_f64.hip): the formulas, profiles and conventions
+ * above (a Matern-1/2 pair at r = 0 adds 0 to the gradient; grad_x2 is plx_exact_grad_f64 with the roles swapped).
+ * x1, x2, v, g, out and grad_x1 are double, row-major, contiguous, device memory, 8-byte aligned; every operation is a
+ * double operation (exp and sqrt in double, direct differences, each tile of 64 rows of x2 summed apart from the running
+ * sum): nothing is rounded through fp32.  The limits, the argument checks, their order and their return codes are those
+ * of plx_exact_mvm / plx_exact_grad, all made before any GPU work.
+ * Stateless: d_work is the caller's, at least plx_exact_work_bytes_f64(n1, n2, d, t) bytes (a multiple of 8, monotone in
+ * every size, at most 16 MiB; -1 exactly where plx_exact_work_bytes refuses), so nothing is allocated and the calls are
+ * graph-capturable.  Deterministic: no float atomics, every output element is written by one thread, two identical calls
+ * are bit-equal.
+ * plx_exact_splits_f64: the number of slices the j range of that call is cut into (1: written directly, no workspace
+ * used; > 1: slabs [splits][n1][t or d] of doubles in d_work, summed in slice order by a second kernel); -1 where
+ * plx_exact_work_bytes_f64 refuses.  A host function, and the one the launch itself calls.  The slabs are doubles under
+ * the same 16 MiB, so a call may be cut into fewer slices than the fp32 call of the same sizes.
+ */
+int64_t plx_exact_work_bytes_f64(int64_t n1, int64_t n2, int d, int t);
+int plx_exact_splits_f64(int64_t n1, int64_t n2, int d, int t);
+int plx_exact_mvm_f64(const double *d_x1, int64_t n1, const double *d_x2, int64_t n2, int d, int profile,
+                      const double *d_v, int t, double *d_out, void *d_work, int64_t work_bytes, void *stream);
+int plx_exact_grad_f64(const double *d_x1, int64_t n1, const double *d_x2, int64_t n2, int d, int profile,
+                       const double *d_g, const double *d_v, int t, double *d_grad_x1, void *d_work,
+                       int64_t work_bytes, void *stream);
 
 /*
  * Preconditioned batched CG: the reference trains with gpytorch.settings.max_preconditioner_size(100)

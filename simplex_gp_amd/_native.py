@@ -113,6 +113,10 @@ _SIGNATURES = {
     "plx_exact_splits": (_i32, [_i64, _i64, _i32, _i32]),
     "plx_exact_mvm": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "plx_exact_grad": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "plx_exact_work_bytes_f64": (_i64, [_i64, _i64, _i32, _i32]),
+    "plx_exact_splits_f64": (_i32, [_i64, _i64, _i32, _i32]),
+    "plx_exact_mvm_f64": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "plx_exact_grad_f64": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
     "plx_pcg_work_floats": (_i64, [_i64, _i32, _i32]),
     "plx_pcg_project": (_i32, [_vp, _i32, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "plx_pcg_apply": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -146,7 +150,8 @@ _SIGNATURES = {
 # Calls a library of this ABI may lack (features detected by symbol: has_symbols): lib() binds them where they exist.
 OPTIONAL_SYMBOLS = frozenset(("plx_pcg_work_doubles", "plx_pcg_gram_f64", "plx_pcg_project_f64", "plx_pcg_apply_f64",
                               "plx_pcg_step_direction_f64", "plx_lanczos_work_doubles", "plx_lanczos_shape_f64",
-                              "plx_lanczos_step_f64"))
+                              "plx_lanczos_step_f64", "plx_exact_work_bytes_f64", "plx_exact_splits_f64", "plx_exact_mvm_f64",
+                              "plx_exact_grad_f64"))
 
 
 def declared_symbols():

@@ -1,4 +1,5 @@
-"""The exact kernel MVM (plx_exact_mvm / plx_exact_grad, HIP) behind the same operator surface as the lattice.
+"""The exact kernel MVM (plx_exact_mvm / plx_exact_grad and their _f64 twins, HIP) behind the same operator surface as
+the lattice.
 
     exact_matmul(x1, x2, v, profile)   K(x1, x2) @ v, autograd for v, x1 and x2; nothing N x N is stored
     ExactLazyKernel                    K(x1, x2) known through its action (the protocol of SquareLazyLattice)
@@ -8,7 +9,9 @@
 
 The profiles are the project's own (stencil.py): "rbf" is exp(-d2), "matern12/32/52" the Matern-nu profiles of
 r = sqrt(d2).  This is what the lattice stands in for, so the exact operator measures the lattice's approximation error
-and gives the like-for-like "lattice vs exact on the same GPU" speed figure.  There is no CPU path.
+and gives the like-for-like "lattice vs exact on the same GPU" speed figure.  float32 tensors run the fp32 kernels,
+float64 tensors the double ones (plx_exact_f64.hip: every operation in double, so torch.autograd.gradcheck applies); the
+three tensors of a call share one dtype.  There is no CPU path.
 """
 import ctypes
 
@@ -18,6 +21,7 @@ from torch.autograd import Function
 from . import _native as nv
 from .gp_compat import Kernel, LazyTensor
 
+F64_SYMBOLS = ("plx_exact_work_bytes_f64", "plx_exact_splits_f64", "plx_exact_mvm_f64", "plx_exact_grad_f64")
 PROFILES = {"rbf": nv.PROFILE_RBF, "matern12": nv.PROFILE_MATERN12, "matern32": nv.PROFILE_MATERN32,
             "matern52": nv.PROFILE_MATERN52}
 _MATERN_PROFILE = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
@@ -30,11 +34,16 @@ def _profile_code(profile):
 
 
 def _check(x1, x2, v):
+    floats = {t.dtype for t in (x1, x2, v) if isinstance(t, torch.Tensor)}
+    if floats == {torch.float32, torch.float64}:              # wherever the tensors live: as the lattice's filter
+        raise TypeError(f"x1, x2 and v must share one dtype (got {x1.dtype}, {x2.dtype}, {v.dtype})")
     for name, t in (("x1", x1), ("x2", x2), ("v", v)):
         if not (isinstance(t, torch.Tensor) and t.is_cuda):
             raise ValueError(f"simplex_gp_amd has no CPU path: {name} must live on an MI355X (cuda) device")
-        if t.dtype != torch.float32:
-            raise TypeError(f"float32 only (got {name} {t.dtype})")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"float32 or float64 only (got {name} {t.dtype})")
+    if x1.dtype == torch.float64 and not nv.has_symbols(*F64_SYMBOLS):
+        raise TypeError("float64 tensors need a libplx.so that exports " + ", ".join(F64_SYMBOLS) + ": rebuild it")
     if x1.dim() != 2 or x2.dim() != 2 or v.dim() != 2:
         raise ValueError(f"x1 [n1, d], x2 [n2, d] and v [n2, t] are matrices (got {tuple(x1.shape)}, {tuple(x2.shape)}, "
                          f"{tuple(v.shape)})")
@@ -47,11 +56,16 @@ def _check(x1, x2, v):
 
 
 def _call(fn, x1, x2, a, b, t, out):
-    """One plx_exact_mvm (b is None) or plx_exact_grad on the current stream, the workspace from torch's allocator."""
+    """One plx_exact_mvm (b is None) or plx_exact_grad on the current stream, the workspace from torch's allocator; the
+    _f64 entry points and their workspace bound where the tensors are float64."""
     L = nv.lib()
     n1, d = x1.shape
     n2 = x2.shape[0]
-    nbytes = L.plx_exact_work_bytes(n1, n2, d, t)
+    f64 = x1.dtype == torch.float64
+    work_bytes, mvm, grad = ((L.plx_exact_work_bytes_f64, L.plx_exact_mvm_f64, L.plx_exact_grad_f64) if f64 else
+                             (L.plx_exact_work_bytes, L.plx_exact_mvm, L.plx_exact_grad))
+    who = ("plx_exact_mvm" if b is None else "plx_exact_grad") + ("_f64" if f64 else "")
+    nbytes = work_bytes(n1, n2, d, t)
     if nbytes < 0:
         raise ValueError(f"sizes outside the exact kernel's limits: n1 = {n1}, n2 = {n2}, d = {d}, t = {t}")
     work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x1.device)
@@ -59,17 +73,15 @@ def _call(fn, x1, x2, a, b, t, out):
     with torch.cuda.device(x1.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(x1.device).cuda_stream)
         if b is None:
-            rc = L.plx_exact_mvm(ptr(x1), n1, ptr(x2), n2, d, fn, ptr(a), t, ptr(out), ptr(work), work.numel(), stream)
-            nv.check(rc, "plx_exact_mvm")
+            rc = mvm(ptr(x1), n1, ptr(x2), n2, d, fn, ptr(a), t, ptr(out), ptr(work), work.numel(), stream)
         else:
-            rc = L.plx_exact_grad(ptr(x1), n1, ptr(x2), n2, d, fn, ptr(a), ptr(b), t, ptr(out), ptr(work), work.numel(),
-                                  stream)
-            nv.check(rc, "plx_exact_grad")
+            rc = grad(ptr(x1), n1, ptr(x2), n2, d, fn, ptr(a), ptr(b), t, ptr(out), ptr(work), work.numel(), stream)
+        nv.check(rc, who)
     return out
 
 
 def _mvm(x1, x2, v, code):
-    out = torch.empty((x1.shape[0], v.shape[1]), dtype=torch.float32, device=x1.device)
+    out = torch.empty((x1.shape[0], v.shape[1]), dtype=x1.dtype, device=x1.device)
     return _call(code, x1.contiguous(), x2.contiguous(), v.contiguous(), None, v.shape[1], out)
 
 
@@ -105,8 +117,9 @@ class ExactMatmul(Function):
 
 
 def exact_matmul(x1, x2, v, profile="rbf"):
-    """K(x1, x2) @ v, K[i, j] = k(|x1_i - x2_j|^2) with k one of PROFILES, on the GPU (fp32; positions already divided by
-    the lengthscale).  v: [n2, t] or [n2].  Differentiable in x1, x2 and v."""
+    """K(x1, x2) @ v, K[i, j] = k(|x1_i - x2_j|^2) with k one of PROFILES, on the GPU (positions already divided by the
+    lengthscale).  x1, x2 and v share one dtype, float32 or float64, and the product is evaluated and returned in it.
+    v: [n2, t] or [n2].  Differentiable in x1, x2 and v."""
     code = _profile_code(profile)
     vec = isinstance(v, torch.Tensor) and v.dim() == 1
     v2 = v.unsqueeze(-1) if vec else v
@@ -173,15 +186,15 @@ def MaternExact(*args, nu=1.5, **kwargs):
 
 def exact_twin(lattice_kernel):
     """The ExactKernel with the profile and the lengthscale values of `lattice_kernel` (made by RBFLattice,
-    BilateralKernel or MaternLattice), on the same device.  A LatticeAccelerated built from any other callable has no
-    known profile: ValueError."""
+    BilateralKernel or MaternLattice), on the same device and in the same dtype (the twin of a double model's kernel is a
+    double kernel).  A LatticeAccelerated built from any other callable has no known profile: ValueError."""
     profile = getattr(lattice_kernel, "profile", None)
     if profile not in PROFILES:
         raise ValueError("exact_twin: the kernel's profile is not one of the project's (build it with RBFLattice, "
                          "BilateralKernel or MaternLattice)")
     ls = lattice_kernel.lengthscale.detach()
     twin = ExactKernel(profile, ard_num_dims=getattr(lattice_kernel, "ard_num_dims", None))
-    twin = twin.to(ls.device)
+    twin = twin.to(device=ls.device, dtype=ls.dtype)
     twin.lengthscale = ls
     return twin
 
