@@ -1,5 +1,5 @@
 """float64 references, error measures, the kernel-family table and the case list for the exact kernel MVM
-(plx_exact.hip).  Plain numpy on the CPU: tests/test_exact64.py checks these helpers without a GPU,
+(plx_exact_kernels.h with T = float).  Plain numpy on the CPU: tests/test_exact64.py checks these helpers without a GPU,
 tests/test_exact_fp64.py holds the kernels against them.
 
 The measure follows lattice64 / solver64.entry_ratio: every output entry is compared with its float64 value in units
@@ -8,7 +8,7 @@ of a yardstick T, the sum of the absolute values of the terms that entry adds up
 sqrt(3) r, sqrt(5) r for the Materns): the kernel evaluates __expf of an fp32 argument, a relative rounding of the
 argument is an absolute error a in the exponent, so a far pair is legitimately less accurate relative to its own size
 than a near one.  The references take the SAME fp32 values the kernel receives and evaluate the formulas in the header
-of plx_exact.hip by direct differences in float64."""
+of plx_exact_kernels.h by direct differences in float64."""
 import collections
 import os
 import re
@@ -19,7 +19,7 @@ import numpy as np
 from tests.solver64 import FLT_MIN, entry_ratio, f64  # noqa: F401  (entry_ratio is this module's measure too)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "simplex_gp_amd", "csrc", "plx_exact.hip")
+SOURCE = os.path.join(ROOT, "simplex_gp_amd", "csrc", "plx_exact_kernels.h")
 
 PROFILES = ("rbf", "matern12", "matern32", "matern52")          # index = PLX_PROFILE_*
 DPS = (4, 8, 12, 16, 20, 24, 32)
@@ -98,7 +98,7 @@ def grad_floor(x1, x2, g, v):
     return np.shape(x2)[0] * FLT_MIN * span * float(np.abs(f64(g)).sum(1).max()) * float(np.abs(f64(v)).max())
 
 
-# ---- which kernel a call runs: ex_dp / ex_tc of plx_exact.hip, restated ---------------------------------------------------
+# ---- which kernel a call runs: ex_dp / ex_tc of plx_exact_kernels.h, restated (for both scalar types) ----------------------
 def ex_dp(d):
     for dp in DPS[:-1]:
         if d <= dp:
@@ -138,13 +138,14 @@ def missing_coverage(reached):
 
 
 def parse_source(path=SOURCE):
-    """What plx_exact.hip holds: {"kernels": the __global__ kernel names, "dp" / "tc": the template values the switches of
-    ex_dispatch_dp / ex_dispatch_tc launch (case N must launch <N>), "dp_rule" / "tc_rule": ex_dp / ex_tc as
-    ([(bound, value) ...], default), "profiles": the PLX_PROFILE_* names that have a Profile<> specialisation, and
-    "dispatched": those ex_run dispatches}."""
+    """What plx_exact_kernels.h holds, for both scalar types (tests/exact_f64.py reads it too): {"kernels": the __global__ kernel
+    names, "dp" / "tc": the template values the switches of ex_dispatch_dp / ex_dispatch_tc launch (case N must launch
+    <N>), "dp_rule" / "tc_rule": ex_dp / ex_tc as ([(bound, value) ...], default), "profiles": the PLX_PROFILE_* names that
+    have a Profile<> specialisation, "dispatched": those ex_run dispatches, "threads" / "split_j" / "max_splits": the
+    constants of those names, and "tile": {scalar type: rows of the LDS tile}}."""
     text = re.sub(r"//[^\n]*", "", open(path).read())
     found = {"kernels": set(re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s*)?void\s+(\w+)\s*\(", text))}
-    for key, callee in (("dp", r"ex_dispatch_tc<PROF,\s*"), ("tc", r"ex_launch<PROF,\s*DP,\s*")):
+    for key, callee in (("dp", r"ex_dispatch_tc<T,\s*PROF,\s*"), ("tc", r"ex_launch<T,\s*PROF,\s*DP,\s*")):
         values = set()
         for m in re.finditer(r"(?:case\s+(\d+)|default)\s*:\s*%s(\d+)>" % callee, text):
             assert m.group(1) is None or m.group(1) == m.group(2), m.group(0)
@@ -154,8 +155,13 @@ def parse_source(path=SOURCE):
         body = re.search(r"static int %s\(int %s\)\s*\{(.*?)\n\}" % (fn, arg), text, re.S).group(1)
         steps = [(int(a), int(b)) for a, b in re.findall(r"if \(%s <= (\d+)\) return (\d+);" % arg, body)]
         found[key] = (steps, int(re.search(r"\n\s*return (\d+);\s*$", body).group(1)))
-    found["profiles"] = set(re.findall(r"template\s*<>\s*struct\s+Profile<PLX_PROFILE_(\w+)>", text))
-    found["dispatched"] = set(re.findall(r"ex_dispatch_dp<PLX_PROFILE_(\w+)>", text))
+    found["profiles"] = set(re.findall(r"template\s*<typename T>\s*struct\s+Profile<T,\s*PLX_PROFILE_(\w+)>", text))
+    found["dispatched"] = set(re.findall(r"ex_dispatch_dp<T,\s*PLX_PROFILE_(\w+)>", text))
+    for key, name in (("threads", "kExThreads"), ("split_j", "kExSplitJ"), ("max_splits", "kExMaxSplits")):
+        found[key] = int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
+    tiles = re.findall(r"struct ExScalar<(\w+)>\s*\{[^}]*?constexpr int kTileJ = (\d+);", text)
+    found["tile"] = {scalar: int(rows) for scalar, rows in tiles}
+    assert len(found["tile"]) == len(tiles)
     return found
 
 
@@ -221,7 +227,9 @@ SPLIT_EMPTY = (8, 524799, 3, 1, 1024)              # (b) 1024 slices of 513 rows
 SPLIT_CAP = (257, 140001, 3, 64, 255)              # (c) n2 / 512 = 273 slices fit the row bound, the 16 MB cap allows 255
 
 
-def _cases():
+def _cases(n2_edges, empty_group):
+    """The edge and ragged-split cases of every (kind, profile, DP) and the SPLIT_EMPTY ones, for a kernel whose n2 edges
+    (around its LDS tile) are n2_edges; empty_group names the group of a SPLIT_EMPTY case ("{kind}" is filled in)."""
     cases = []
     for ki, kind in enumerate(KINDS):
         for pi, profile in enumerate(PROFILES):
@@ -232,20 +240,24 @@ def _cases():
                 for t in T_EDGES:
                     for d in D_ENDS[dp]:
                         cases.append(Case(group, kind, profile, d, t, N1_EDGES[(idx + rot) % 4],
-                                          N2_EDGES[(idx + N2_STARTS[rot % 4]) % 5], DATA[(idx + idx // 4 + rot) % 4]))
+                                          n2_edges[(idx + N2_STARTS[rot % 4]) % 5], DATA[(idx + idx // 4 + rot) % 4]))
                         idx += 1
                 # (a) the ragged split: every TC in the forward, one per (profile, DP) in the gradient (TC in rotation)
                 for ti, t in enumerate(T_RAGGED if kind == "mvm" else (T_RAGGED[rot % 4],)):
                     cases.append(Case(group, kind, profile, D_ENDS[dp][(ti + rot) % 2], t, *SPLIT_RAGGED, DATA[(ti + rot) % 3]))
     n1, n2, d, t, _ = SPLIT_EMPTY
-    cases += [Case("split-empty", kind, p, d, t, n1, n2, "range") for kind, p in
+    cases += [Case(empty_group.format(kind=kind), kind, p, d, t, n1, n2, "range") for kind, p in
               (("mvm", "rbf"), ("mvm", "matern32"), ("grad", "matern12"), ("grad", "matern52"))]
-    n1, n2, d, t, _ = SPLIT_CAP
-    cases += [Case("split-cap-mvm", "mvm", "matern52", d, t, n1, n2, "range"),
-              Case("split-cap-grad", "grad", "rbf", d, t, n1, n2, "range")]
     return cases
 
 
-CASES = _cases()
+def cap_cases(split_cap):
+    """The two cases of a SPLIT_CAP shape (n1, n2, d, t, splits)."""
+    n1, n2, d, t, _ = split_cap
+    return [Case("split-cap-mvm", "mvm", "matern52", d, t, n1, n2, "range"),
+            Case("split-cap-grad", "grad", "rbf", d, t, n1, n2, "range")]
+
+
+CASES = _cases(N2_EDGES, "split-empty") + cap_cases(SPLIT_CAP)
 GROUPS = list(dict.fromkeys(c.group for c in CASES))
 EDGE_GROUPS = [g for g in GROUPS if not g.startswith("split-")]      # one per (kind, profile, DP)

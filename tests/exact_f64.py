@@ -1,5 +1,5 @@
 """longdouble references, the derived bars, the kernel-family table and the case list for the float64 exact kernel MVM
-(plx_exact_f64.hip).  Plain numpy on the CPU: tests/test_exact_f64_host.py checks these helpers without a GPU,
+(plx_exact_kernels.h with T = double).  Plain numpy on the CPU: tests/test_exact_f64_host.py checks these helpers without a GPU,
 tests/test_exact_f64_gpu.py holds the kernels against them.
 
 The measure is exact64's: every output entry is compared with its reference in units of a yardstick T, the sum of the
@@ -27,28 +27,25 @@ The bars are derived, never measured (bar()).  u = 2^-53.  An entry is off, to f
                     column blocks of t: tiles * ceil(t / TC) additions; the forward's running sum is per block)
     splits          one addition per slab
 The reference's own error (2^-64 per operation, 2^-11 u) and the comparison in longdouble add nothing visible."""
-import os
-import re
 import zlib
 
 import numpy as np
 
 from tests import exact64 as x64
-from tests.exact64 import Case, DATA, KINDS, PROFILES  # noqa: F401
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "simplex_gp_amd", "csrc", "plx_exact_f64.hip")
+# what does not depend on the scalar type is exact64's: the ladders and the family table, the edges of every size but n2
+# (the tile differs), two of the three named split shapes, and the one parser of the one source
+from tests.exact64 import (Case, DATA, KINDS, PROFILES, DPS, TCS, ex_dp, ex_tc, family, FAMILIES, SLAB_FAMILIES,  # noqa: F401
+                           missing_coverage, parse_source, D_ENDS, T_EDGES, N1_EDGES, N2_STARTS, T_RAGGED, SPLIT_RAGGED,
+                           SPLIT_EMPTY)
 
 LD = np.longdouble
 U = 2.0 ** -53
 DBL_MIN = float(np.finfo(np.float64).tiny)
-TILE = 64                                            # kEx64TileJ
-THREADS = 256                                        # kEx64Threads
-SPLIT_J = 512                                        # kEx64SplitJ
-MAX_SPLITS = 1024                                    # kEx64MaxSplits
+TILE = 64                                            # ExScalar<double>::kTileJ
+THREADS = 256                                        # kExThreads
+SPLIT_J = 512                                        # kExSplitJ
+MAX_SPLITS = 1024                                    # kExMaxSplits
 WORK_CAP_BYTES = 16 << 20
-DPS = (4, 8, 12, 16, 20, 24, 32)                     # the double ladders (the fp32 ones are kept)
-TCS = (1, 4, 8, 16)
 C_MVM = 12
 BLOCK_PAIRS = 1 << 20                                # longdouble differences held at a time: n1 * block * d
 PERTURB = 2.0 ** -30
@@ -142,45 +139,6 @@ def entry_ratio(got, want, T, floor=0.0):
     return float((err[~zero] / T[~zero]).max()) if np.any(~zero) else 0.0
 
 
-# ---- which kernel a call runs: ex64_dp / ex64_tc of plx_exact_f64.hip, restated -----------------------------------------
-def ex_dp(d):
-    for dp in DPS[:-1]:
-        if d <= dp:
-            return dp
-    return DPS[-1]
-
-
-def ex_tc(t):
-    for tc in TCS[:-1]:
-        if t <= tc:
-            return tc
-    return TCS[-1]
-
-
-def family(kind, profile, d, t, splits):
-    """(kind, profile, DP, TC, "direct" | "slabs"); splits is what plx_exact_splits_f64 returns for the call."""
-    assert kind in KINDS and profile in PROFILES and splits >= 1
-    return (kind, profile, ex_dp(d), ex_tc(t), "slabs" if splits > 1 else "direct")
-
-
-FAMILIES = [(kind, p, dp, tc) for kind in KINDS for p in PROFILES for dp in DPS for tc in TCS]      # the 224 instantiations
-# where the slab path must be reached as well: the slab stride is n1 t in the forward (every TC) and n1 d in the gradient
-SLAB_FAMILIES = [("mvm", "TC", tc) for tc in TCS] + [("grad", "DP", dp) for dp in DPS]
-
-
-def missing_coverage(reached):
-    """What a set of family() results leaves out: instantiations of FAMILIES never run, and (kind, profile, axis, value)
-    of SLAB_FAMILIES, per profile, never run on the slab path."""
-    reached = set(reached)
-    missing = sorted(set(FAMILIES) - {f[:4] for f in reached})
-    slabs = [f for f in reached if f[4] == "slabs"]
-    for kind, axis, value in SLAB_FAMILIES:
-        for p in PROFILES:
-            if not any(f[0] == kind and f[1] == p and f[2 if axis == "DP" else 3] == value for f in slabs):
-                missing.append((kind, p, axis, value, "slabs"))
-    return missing
-
-
 def bar(kind, d, t, n2, splits):
     """The derived bound on |got - want| / T of one call (module docstring)."""
     dp, tc = ex_dp(d), ex_tc(t)
@@ -189,27 +147,6 @@ def bar(kind, d, t, n2, splits):
     if kind == "mvm":
         return (TILE + dp + C_MVM + tiles + splits) * U
     return (TILE + dp + C_MVM + tc + 2 + tiles * -(-t // tc) + splits) * U
-
-
-def parse_source(path=SOURCE):
-    """What plx_exact_f64.hip holds: the template values its two dispatch switches launch, its ex64_dp / ex64_tc rules as
-    ([(bound, value) ...], default), and the constants the case list is built around."""
-    text = re.sub(r"//[^\n]*", "", open(path).read())
-    found = {}
-    for key, callee in (("dp", r"ex64_dispatch_tc<PROF,\s*"), ("tc", r"ex64_launch<PROF,\s*DP,\s*")):
-        values = set()
-        for m in re.finditer(r"(?:case\s+(\d+)|default)\s*:\s*%s(\d+)>" % callee, text):
-            assert m.group(1) is None or m.group(1) == m.group(2), m.group(0)
-            values.add(int(m.group(2)))
-        found[key] = values
-    for key, fn, arg in (("dp_rule", "ex64_dp", "d"), ("tc_rule", "ex64_tc", "t")):
-        body = re.search(r"static int %s\(int %s\)\s*\{(.*?)\n\}" % (fn, arg), text, re.S).group(1)
-        steps = [(int(a), int(b)) for a, b in re.findall(r"if \(%s <= (\d+)\) return (\d+);" % arg, body)]
-        found[key] = (steps, int(re.search(r"\n\s*return (\d+);\s*$", body).group(1)))
-    for key, name in (("tile", "kEx64TileJ"), ("threads", "kEx64Threads"), ("split_j", "kEx64SplitJ"),
-                      ("max_splits", "kEx64MaxSplits")):
-        found[key] = int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
-    return found
 
 
 # ---- data ------------------------------------------------------------------------------------------------------------
@@ -239,50 +176,19 @@ def off_fp32_grid(a):
 
 
 # ---- cases -----------------------------------------------------------------------------------------------------------
-D_ENDS = {4: (1, 4), 8: (5, 8), 12: (9, 12), 16: (13, 16), 20: (17, 20), 24: (21, 24), 32: (25, 32)}
-T_EDGES = (1, 2, 4, 5, 8, 9, 16, 17, 32, 33)       # both ends of every TC, and one, two and three column blocks
-N1_EDGES = (1, 255, 256, 257)                      # one row; the 256-row workgroup with a dead lane, full, and one row over
 N2_EDGES = (65, 1, 150, 63, 64)                    # the 64-row LDS tile: one row over, one row, three tiles, below, full
-N2_STARTS = (0, 1, 2, 4)                           # rotations of N2_EDGES whose first two entries include more than one tile
-T_RAGGED = (1, 3, 7, 19)                           # one t per TC, none a multiple of it (19: two column blocks)
 # The named split shapes (n1, n2, d, t, splits), derived for the double workspace (slabs of doubles under 16 MiB = 2^21
-# doubles; a slice covers at least 512 j; at most 1024 slices and 524288 slab rows):
+# doubles; a slice covers at least 512 j; at most 1024 slices and 524288 slab rows).  exact64's SPLIT_RAGGED and
+# SPLIT_EMPTY hold here as well:
 # (a) two slices, neither a multiple of the 64-row tile, two row blocks: n2 // 512 = 2 slices of 750 = 11 * 64 + 46 rows
-SPLIT_RAGGED = (257, 1500)
 # (b) the maximum split count with the last slice empty: n2 // 512 = 1024 slices of ceil(524799 / 1024) = 513 rows, and
 #     1023 * 513 = 524799 = n2; the gradient's slabs (1024 * 8 * 3 doubles) fill the workspace to the last double
-SPLIT_EMPTY = (8, 524799, 3, 1, 1024)
 # (c) a split count set by the 16 MiB cap: 2^21 doubles / 64 columns = 32768 slab rows = 127 slices of 257 rows (128 do
 #     not fit), where n2 // 512 = 136 would be allowed
 SPLIT_CAP = (257, 70001, 3, 64, 127)
 CAP_ROWS = (0, 1, 255, 256)                        # the rows of (c) judged against longdouble: both workgroups, the dead-lane edge
 
-
-def _cases():
-    cases = []
-    for ki, kind in enumerate(KINDS):
-        for pi, profile in enumerate(PROFILES):
-            for di, dp in enumerate(DPS):
-                group = f"{kind}-{profile}-dp{dp}"
-                rot = ki + pi + di
-                idx = 0         # n1 turns with idx, the data kind with idx + idx // 4: the 20 cases hold all 16 (n1, data) pairs
-                for t in T_EDGES:
-                    for d in D_ENDS[dp]:
-                        cases.append(Case(group, kind, profile, d, t, N1_EDGES[(idx + rot) % 4],
-                                          N2_EDGES[(idx + N2_STARTS[rot % 4]) % 5], DATA[(idx + idx // 4 + rot) % 4]))
-                        idx += 1
-                # (a) the ragged split: every TC in the forward, one per (profile, DP) in the gradient (TC in rotation)
-                for ti, t in enumerate(T_RAGGED if kind == "mvm" else (T_RAGGED[rot % 4],)):
-                    cases.append(Case(group, kind, profile, D_ENDS[dp][(ti + rot) % 2], t, *SPLIT_RAGGED, DATA[(ti + rot) % 3]))
-    n1, n2, d, t, _ = SPLIT_EMPTY
-    cases += [Case(f"split-empty-{kind}", kind, p, d, t, n1, n2, "range") for kind, p in
-              (("mvm", "rbf"), ("mvm", "matern32"), ("grad", "matern12"), ("grad", "matern52"))]
-    return cases
-
-
-CASES = _cases()
-n1_, n2_, d_, t_, _s = SPLIT_CAP
-CAP_CASES = [Case("split-cap-mvm", "mvm", "matern52", d_, t_, n1_, n2_, "range"),
-             Case("split-cap-grad", "grad", "rbf", d_, t_, n1_, n2_, "range")]
+CASES = x64._cases(N2_EDGES, "split-empty-{kind}")
+CAP_CASES = x64.cap_cases(SPLIT_CAP)
 GROUPS = list(dict.fromkeys(c.group for c in CASES))
 EDGE_GROUPS = [g for g in GROUPS if not g.startswith("split-")]      # one per (kind, profile, DP)

@@ -1,5 +1,5 @@
 """tests/exact64.py itself, on the CPU: the float64 references of the exact kernel MVM against a naive double loop and a
-finite difference, the error measure, the family table against plx_exact.hip, and the acceptance test of the case list of
+finite difference, the error measure, the family table against plx_exact_kernels.h, and the acceptance test of the case list of
 tests/test_exact_fp64.py (which instantiation and which path every case runs is a host-side fact: plx_exact_splits)."""
 import math
 
@@ -115,12 +115,14 @@ def test_data_of_a_case():
 
 
 def test_exact_families_name_every_kernel_and_template_value():
-    """FAMILIES is exactly profiles x DP x TC of the two templated kernels as plx_exact.hip dispatches them, the slab kernel
+    """FAMILIES is exactly profiles x DP x TC of the two templated kernels as plx_exact_kernels.h dispatches them, the slab kernel
     is the only other kernel, and ex_dp / ex_tc are restated correctly: a new value or profile fails here until exact64
     (and so a case) names it."""
     src = x64.parse_source()
     assert src["kernels"] == set(x64.KERNELS.values()) | {x64.SLAB_KERNEL}
     assert src["dp"] == set(x64.DPS) and src["tc"] == set(x64.TCS)
+    tile = src["tile"]["float"]                                  # the fp32 tile is what N2_EDGES is built around
+    assert tile == 128 and set(x64.N2_EDGES) == {1, tile - 1, tile, tile + 1, 300} and 300 > 2 * tile
     assert src["profiles"] == src["dispatched"] == {p.upper() for p in x64.PROFILES}
     assert len(x64.FAMILIES) == 224 == len(set(x64.FAMILIES))
     assert set(x64.FAMILIES) == {(k, p, dp, tc) for k in x64.KERNELS for p in x64.PROFILES for dp in src["dp"] for tc in src["tc"]}

@@ -156,7 +156,7 @@ def test_exact_twin_follows_the_dtype():
 def test_source_matches_the_restated_ladders():
     src = xf.parse_source()
     assert src["dp"] == set(xf.DPS) and src["tc"] == set(xf.TCS)
-    assert src["tile"] == xf.TILE and src["threads"] == xf.THREADS and src["split_j"] == xf.SPLIT_J and src["max_splits"] == xf.MAX_SPLITS
+    assert src["tile"] == {"float": 128, "double": xf.TILE} and xf.TILE == 64 and src["threads"] == xf.THREADS and src["split_j"] == xf.SPLIT_J and src["max_splits"] == xf.MAX_SPLITS
     for rule, fn, top in ((src["dp_rule"], xf.ex_dp, 32), (src["tc_rule"], xf.ex_tc, 70)):
         steps, default = rule
         for z in range(1, top + 1):

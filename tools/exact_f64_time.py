@@ -35,7 +35,7 @@ DPS, TCS = (4, 8, 12, 16, 20, 24, 32), (1, 4, 8, 16)
 
 
 def model_pairs_per_s_f64(d, t, profile):
-    """The inner loop of exact64_mvm_kernel as compiled: per pair and lane 2 DP double-rate
+    """The inner loop of exact_mvm_kernel<double, ...> as compiled: per pair and lane 2 DP double-rate
     instructions for the distance, 20 for the software exp (v_mul, v_rndne, 14 FMAs of the reduction and the polynomial,
     v_cvt_i32_f64, v_ldexp_f64, two compares), TC FMAs for the contraction, and 13 single-rate ones (the polynomial's
     constants as v_mov_b64, the range selects, the loop); a Matern adds 17 double-rate (v_rsq_f64 and its Newton steps,
