@@ -10,8 +10,8 @@
 //
 // Pipeline (all arrays "entry"-indexed are SoA [r][p], r = simplex corner,
 // p = point IN LATTICE ORDER, so that every wave access is a contiguous run):
-//   order    per point: rounded lattice coordinates -> 64-bit key (shard id, then
-//            the coordinates lexicographically); radix sort -> perm.  Points that
+//   order    per point: coordinates of its lattice cell -> 64-bit key (shard id, then
+//            the coordinates along their Z-curve); radix sort -> perm.  Points that
 //            share or neighbour a simplex become neighbours in memory, which is
 //            what makes the splat / slice / blur gathers hit the same cache lines
 //            (measured: warm MVM 159 -> 118 us at N=1e6, d=8)
@@ -254,11 +254,74 @@ __device__ __forceinline__ void elevate(const float (&pos)[D], const ScaleArgs &
     el[0] = el[1] + 2.0f * pos[0] * sf.v[0];
 }
 
+// h:405-457: the nearest zero-colour vertex of an elevated point (gr: multiples of d+1 that sum to zero once the rank
+// fix-up has run) and the rank of every coordinate's residual.  Shared by the embedding and the point order, so a point
+// is ordered by the very cell it is embedded in.  Returns true when a coordinate left the int16 key range (or is NaN / Inf).
+template <int D>
+__device__ __forceinline__ bool nearest_vertex(const float (&el)[D + 1], int (&gr)[D + 1], int (&rk)[D + 1])
+{
+    constexpr int D1 = D + 1;
+    // h:405-423
+    constexpr float scale = 1.0f / (float)D1;
+    constexpr float limit = 32767.0f - 2.0f * (float)D1;   // room for the fix-up and the canonical offsets
+    int sum = 0;
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < D1; ++i) {
+        float v = el[i] * scale;
+        float up = ceilf(v) * (float)D1;
+        float down = floorf(v) * (float)D1;
+        float g = (up - el[i] < el[i] - down) ? up : down;
+        if (!(fabsf(g) <= limit)) { bad = true; g = 0.f; }   // also catches NaN / Inf
+        gr[i] = (int)g;
+        sum += gr[i];
+    }
+    sum = (int)((float)sum * scale);   // int *= float, h:423
+
+    // h:427-433
+#pragma unroll
+    for (int i = 0; i < D1; ++i) rk[i] = 0;
+    {
+        float df[D1];
+#pragma unroll
+        for (int i = 0; i < D1; ++i) df[i] = el[i] - (float)gr[i];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = i + 1; j <= D; ++j) {
+                bool lt = df[i] < df[j];
+                rk[i] += lt ? 1 : 0;
+                rk[j] += lt ? 0 : 1;
+            }
+    }
+
+    // h:435-457
+    if (sum > 0) {
+#pragma unroll
+        for (int i = 0; i < D1; ++i) {
+            bool wrap = rk[i] >= D1 - sum;
+            gr[i] -= wrap ? D1 : 0;
+            rk[i] += wrap ? (sum - D1) : sum;
+        }
+    } else if (sum < 0) {
+#pragma unroll
+        for (int i = 0; i < D1; ++i) {
+            bool wrap = rk[i] < -sum;
+            gr[i] += wrap ? D1 : 0;
+            rk[i] += wrap ? (D1 + sum) : sum;
+        }
+    }
+    return bad;
+}
+
 // ----------------------------------------------------------------------------
-// order: sort key of a point = (shard, rounded lattice coordinates bit-interleaved along their Z-curve).  The keys are
-// COMPACT: a first pass finds the range of every rounded coordinate, the host reads
+// order: sort key of a point = (shard, coordinates of its lattice cell bit-interleaved along their Z-curve).  The cell is
+// the fixed-up nearest zero-colour vertex the embedding uses (nearest_vertex), in units of d+1 -- not the plainly rounded
+// coordinates, which name a different cell for every point whose rounded coordinates do not sum to zero (55 % of the points
+// at N = 1e6, d = 8, l = 1: 94,840 rounded "cells" over 44,428 real ones, a fifth more block rows).  The keys are
+// COMPACT: a first pass finds the range of every cell coordinate, the host reads
 // the 2 (d+1) numbers back through the mailbox (read_back: no stream synchronisation) and gives every coordinate exactly
-// the bits its range needs, so the radix sort runs over the significant bits only (N = 1e6, d = 8, l = 1: 36 bits
+// the bits its range needs, so the radix sort runs over the significant bits only (N = 1e6, d = 8, l = 1: 27 bits
 // instead of 63).  Outliers cost bits, never correctness: past 62 key bits the widest coordinates lose low bits.
 
 constexpr int kMaxOrderCoords = 16;
@@ -271,7 +334,9 @@ struct OrderArgs {
     int lo[kMaxOrderCoords], bits[kMaxOrderCoords], drop[kMaxOrderCoords];   // per coordinate: smallest value, key bits, low bits dropped
 };
 
-// rounded lattice coordinates of a point (the cell of its nearest zero-colour vertex, in units of d+1)
+// lattice cell of a point: the coordinates of its (fixed-up) nearest zero-colour vertex in units of d+1 (exact: they are
+// multiples of d+1).  A coordinate out of range or NaN counts as 0 here (nearest_vertex) and the point sorts wherever that
+// puts it: it is embed_kernel that rejects it.
 template <int D>
 __device__ __forceinline__ void order_coords(const float *__restrict__ x, int p, const ScaleArgs &sf, int (&q)[D + 1])
 {
@@ -280,12 +345,10 @@ __device__ __forceinline__ void order_coords(const float *__restrict__ x, int p,
 #pragma unroll
     for (int i = 0; i < D; ++i) pos[i] = x[(size_t)p * D + i];
     elevate<D>(pos, sf, el);
+    int gr[D1], rk[D1];
+    (void)nearest_vertex<D>(el, gr, rk);
 #pragma unroll
-    for (int i = 0; i < D1; ++i) {
-        float c = rintf(el[i] * (1.0f / (float)D1));
-        c = fminf(fmaxf(c, -1.0e6f), 1.0e6f);                // NaN -> -1e6 (fmaxf), rejected later by embed
-        q[i] = (int)c;
-    }
+    for (int i = 0; i < D1; ++i) q[i] = gr[i] / D1;
 }
 
 // range[2c] = max q_c, range[2c+1] = max -q_c over all points (range[] preset to a very negative number)
@@ -449,58 +512,10 @@ __global__ __launch_bounds__(kBlock) void embed_kernel(const float *__restrict__
     float el[D1];
     elevate<D>(pos, sf, el);
 
-    // h:405-423
+    // h:405-457
     constexpr float scale = 1.0f / (float)D1;
-    constexpr float limit = 32767.0f - 2.0f * (float)D1;   // room for the fix-up and the canonical offsets
-    int gr[D1];
-    int sum = 0;
-    bool bad = false;
-#pragma unroll
-    for (int i = 0; i < D1; ++i) {
-        float v = el[i] * scale;
-        float up = ceilf(v) * (float)D1;
-        float down = floorf(v) * (float)D1;
-        float g = (up - el[i] < el[i] - down) ? up : down;
-        if (!(fabsf(g) <= limit)) { bad = true; g = 0.f; }   // also catches NaN / Inf
-        gr[i] = (int)g;
-        sum += gr[i];
-    }
-    sum = (int)((float)sum * scale);   // int *= float, h:423
-
-    // h:427-433
-    int rk[D1];
-#pragma unroll
-    for (int i = 0; i < D1; ++i) rk[i] = 0;
-    {
-        float df[D1];
-#pragma unroll
-        for (int i = 0; i < D1; ++i) df[i] = el[i] - (float)gr[i];
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = i + 1; j <= D; ++j) {
-                bool lt = df[i] < df[j];
-                rk[i] += lt ? 1 : 0;
-                rk[j] += lt ? 0 : 1;
-            }
-    }
-
-    // h:435-457
-    if (sum > 0) {
-#pragma unroll
-        for (int i = 0; i < D1; ++i) {
-            bool wrap = rk[i] >= D1 - sum;
-            gr[i] -= wrap ? D1 : 0;
-            rk[i] += wrap ? (sum - D1) : sum;
-        }
-    } else if (sum < 0) {
-#pragma unroll
-        for (int i = 0; i < D1; ++i) {
-            bool wrap = rk[i] < -sum;
-            gr[i] += wrap ? D1 : 0;
-            rk[i] += wrap ? (D1 + sum) : sum;
-        }
-    }
+    int gr[D1], rk[D1];
+    const bool bad = nearest_vertex<D>(el, gr, rk);
 
     // h:460-465.  rank is a permutation of 0..d, so every barycentric cell gets
     // exactly one "+=" and one "-=": bary[k] = delta[rank == d-k] - delta[rank == d+1-k].
@@ -1849,7 +1864,7 @@ static int stage_local(plx_lattice *L, const float *d_ref, hipStream_t stream, i
     if (keep_order) {
         ++L->order_age;
     } else if (g_sort_points) {
-        // range of every rounded coordinate -> exactly the key bits it needs (counters[32 ..] preset to a very negative int)
+        // range of every cell coordinate -> exactly the key bits it needs (counters[32 ..] preset to a very negative int)
         int *range = L->counters.as<int>() + 32;
         PLX_HIP_TRY(hipMemsetAsync(range, 0x80, 2 * kMaxOrderCoords * sizeof(int), stream));
         const int rstride = n >= kOrderSampleMinPoints ? kOrderSample : 1;

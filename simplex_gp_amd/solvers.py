@@ -813,6 +813,30 @@ def batched_cg(matmul, B, max_iter=1000, tol=1e-4, reduce=None, want_tridiag=Fal
 # 4.88 / 4.98 (rank-100 preconditioner: 6.72 / 6.88); N = 1e5: 2.82 / 2.81; N = 3e5: 12.33 / 12.35; N = 1e6: 28.57 / 28.48
 # (preconditioned 35.97 / 35.81): the fold pays where an iteration is launch-bound and costs 0.3-0.5 % where each workgroup's
 # redundant sum over the partials (0.56 MB at N = 1e6) outweighs two 7 us launches.
+REFINE_ABOVE = 10.0      # khat_solve: a converged solve whose TRUE residual is above this many times its tolerance is corrected once
+
+
+def _refine_solution(matmul, B, X, info, matmul_dot, native_pre, cg_args):
+    """One step of iterative refinement behind a converged fp32 solve.  The CG recurrence updates its residual, it does not
+    recompute it, so every step leaves alpha x (rounding of A p) between the two; near convergence on an ill-conditioned system
+    alpha is about 1 / lambda_min and the true residual ends well above the recurrence's (n = 30,000, d = 2, noise 0.0068,
+    tol 1e-4: 2.4e-4 ... 2.6e-3 after ~1,000 iterations, depending on nothing but the order of the fp32 sums:
+    profiles/order_cell_measured.md).  So the residual is computed once (one MVM); where the recurrence says converged and the truth
+    is more than REFINE_ABOVE x tol, the correction A D = B - A X is solved to the remaining factor and added.  Not for runs
+    that want the tridiagonals (they belong to the first solve) and not where REFINE_ABOVE x tol >= 1 (the training tolerance)."""
+    tol = float(cg_args.get("tol", 1e-4))
+    if tol <= 0 or REFINE_ABOVE * tol >= 1 or cg_args.get("want_tridiag") or B.dtype != torch.float32:
+        return X, info
+    R = B - matmul(X)
+    rel = R.norm(dim=0) / B.norm(dim=0).clamp_min(1e-30)
+    worst, claimed = torch.stack([rel.max(), info["residual"].max().to(rel.dtype)]).tolist()
+    if not (claimed <= tol and worst > REFINE_ABOVE * tol):
+        return X, info
+    D, more = batched_cg(matmul, R.contiguous(), matmul_dot=matmul_dot, native_precond=native_pre,
+                         **dict(cg_args, tol=min(1.0, tol / worst)))
+    return X + D, dict(info, iterations=info["iterations"] + more["iterations"], residual=more["residual"] * rel, refined=True)
+
+
 FUSED_CG_STEPS = "auto"
 FUSED_CG_MAX_ROWS = 65536
 
@@ -1168,6 +1192,7 @@ class LatticeGP(nn.Module):
                     fused_dot.partial = lambda V: lat.apply_affine(V, ss, want_dot="partial")
                 sol, info = batched_cg(lambda V: lat.apply_affine(V, ss), rhs_l, matmul_dot=fused_dot, native_precond=native_pre,
                                        **cg_args)
+                sol, info = _refine_solution(lambda V: lat.apply_affine(V, ss), rhs_l, sol, info, fused_dot, native_pre, cg_args)
                 if pad:
                     sol = sol[:, :t].contiguous()
                     info = dict(info, residual=info["residual"][:t])
