@@ -520,13 +520,17 @@ int plx_cg_step_direction(float *d_p, const float *d_r, const float *d_rs_new, c
  * row i + 1 of d_q = w / max(beta_i, 1e-30).  Four launches, two streams of the basis, deterministic (fixed-order sums, no atomics).
  * i + 1 <= plx_lanczos_max_rows() (256); d_work: float [plx_lanczos_work_floats(n)] (< 0: n is larger than the 2,097,152
  * rows the step serves); ld >= n, a multiple of 4, d_q 16-byte aligned (columns n..ld-1 of the basis are never written).
+ * Every argument is checked before any launch, by the checks of plx_lanczos_step_f64 below (one source for both,
+ * csrc/plx_lanczos_kernels.h): PLX_ERR_INVALID also for a pointer off 4-byte alignment and for a d_w with any part
+ * inside rows 0..i+1 of the basis, [d_q, d_q + (i + 2) ld) -- w is read and written while those rows are read and row
+ * i + 1 is written.
  */
 int plx_lanczos_max_rows(void);
 int64_t plx_lanczos_work_floats(int64_t n);
 int plx_lanczos_step(float *d_q, int64_t ld, float *d_w, int64_t n, int i, float *d_alphas, float *d_betas, float *d_work,
                      void *stream);
 /*
- * The same step with every array in double (csrc/plx_lanczos_f64.hip): the recurrence and its order are
+ * The same step with every array in double (csrc/plx_lanczos_kernels.h with T = double): the recurrence and its order are
  * plx_lanczos_step's, the guard of the division is 1e-300 (row i + 1 of d_q = w / max(beta_i, 1e-300)).
  *   d_q       double [rows >= i + 2][ld], row-major, 16-byte aligned, ld >= n and ld % 2 == 0; columns n..ld-1 are never
  *             read for a result and never written

@@ -102,8 +102,8 @@ _F64_SYMBOLS = ("plx_lanczos_work_doubles", "plx_lanczos_shape_f64", "plx_lanczo
 
 
 def _lanczos_native(matmul, v0, steps, check_every):
-    """The recurrence with everything but the MVM in plx_lanczos_step (csrc/plx_lanczos.hip) or, for a float64 v0,
-    plx_lanczos_step_f64 (csrc/plx_lanczos_f64.hip): per step the operator's own launches + 4.  The components along
+    """The recurrence with everything but the MVM in plx_lanczos_step (csrc/plx_lanczos_kernels.h) or, for a float64 v0,
+    plx_lanczos_step_f64 (the same source with T = double): per step the operator's own launches + 4.  The components along
     q_{i-1}, q_i first (the three-term recurrence), then one classical Gram-Schmidt pass against the whole basis built so
     far -- the torch form's order, which is what keeps the pass stable; deterministic.  Basis, coefficients and
     workspace are in v0.dtype; the rows of the basis start on 256-byte boundaries.  None when the library does not serve

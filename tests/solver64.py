@@ -1,5 +1,5 @@
 """float64 references, error measures and the kernel-family table for the native solver kernels (plx_linalg.hip,
-plx_pcg.hip, plx_lanczos.hip).  Plain numpy on the CPU: tests/test_solver64.py checks these helpers without a GPU,
+plx_pcg.hip, plx_lanczos_kernels.h).  Plain numpy on the CPU: tests/test_solver64.py checks these helpers without a GPU,
 tests/test_solver_fp64.py holds the kernels against them.
 
 The measure follows lattice64.terms64 / entry_ratio: every output entry is compared with its float64 value in units of
@@ -15,7 +15,7 @@ TINY = 1e-30            # the max(x, tiny) guard of the CG coefficients (plx_lin
 EPS32 = 2.0 ** -24      # half an ulp of fp32, relative
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("plx_linalg.hip", "plx_pcg.hip", "plx_lanczos.hip")
+SOURCES = ("plx_linalg.hip", "plx_pcg.hip", "plx_lanczos_kernels.h")
 NOT_OURS = ("backward_stack_kernel", "backward_contract_kernel")      # DESIGN section 10 owns them
 
 
@@ -306,25 +306,50 @@ def family_values(name):
     return [int(x) for x in re.findall(r"\d+", m.group(1).split(",")[0])] if m else []
 
 
+def _source(src, root):
+    return re.sub(r"//[^\n]*", "", open(os.path.join(root, "simplex_gp_amd", "csrc", src)).read())
+
+
+def ladder_spans(root=ROOT, src="plx_lanczos_kernels.h"):
+    """{"float": [...], "double": [...]}: the spans of each LzScalar<T>::kLadder, the only values the templated dispatch
+    (lz_dispatch<T, K>: lanczos_launch<T, LzScalar<T>::kLadder[K].span>) instantiates for T."""
+    text = _source(src, root)
+    spans = {}
+    for m in re.finditer(r"struct\s+LzScalar<(\w+)>\s*\{(.*?)\n\};", text, re.S):
+        rungs = re.search(r"kLadder\[\]\s*=\s*\{(.*?)\};", m.group(2), re.S)
+        spans[m.group(1)] = [int(v) for v in re.findall(r"\{\s*(\d+)\s*,", rungs.group(1))]
+    return spans
+
+
 def parse_sources(root=ROOT):
     """(kernels, pairs): every __global__ kernel name of the three sources, and every (kernel, value) pair their
     switch statements dispatch: `case N: kernel<N...>` / `default: kernel<N>`, `case N: launcher<N>(...)` for a host
-    template that launches kernel<SPAN>s, and every PLX_*_CASE(N) invocation of a macro whose body names kernel<...>."""
+    template that launches kernel<SPAN>s, and every PLX_*_CASE(N) invocation of a macro whose body names kernel<...>.
+    A host template over <typename T, int SPAN> that launches kernel<T, SPAN>s and is called with a rung of the type's
+    ladder (`launcher<T, SPAN>` with SPAN = LzScalar<T>::kLadder[K].span) dispatches the spans of the FLOAT ladder: the
+    fp32 families keep their names, kernel<span>; ladder_spans has the double ladder."""
     kernels, pairs = set(), set()
     for src in SOURCES:
-        text = open(os.path.join(root, "simplex_gp_amd", "csrc", src)).read()
-        text = re.sub(r"//[^\n]*", "", text)
+        text = _source(src, root)
         kernels.update(re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s*)?void\s+(\w+)\s*\(", text))
         # host templates that launch kernels with their own template value: launcher -> kernels
-        launchers = {}
-        for m in re.finditer(r"template\s*<int (\w+)>\s*static\s+\w+\s+(\w+)\s*\(", text):
+        launchers, typed = {}, set()
+        for m in re.finditer(r"template\s*<(typename T,\s*)?int (\w+)>\s*static\s+\w+\s+(\w+)\s*\(", text):
             body = text[m.end(): text.find("\n}\n", m.end())]
-            launchers[m.group(2)] = set(re.findall(r"(\w+_kernel)<%s>" % m.group(1), body))
+            launched = set(re.findall(r"(\w+_kernel)<%s%s>" % ("T, " if m.group(1) else "", m.group(2)), body))
+            launchers[m.group(3)] = launched
+            if m.group(1) and launched:
+                typed.add(m.group(3))
         for m in re.finditer(r"(?:case\s+(\d+)|default)\s*:\s*(\w+)<(\d+)[,>]", text):
             value, callee = int(m.group(3)), m.group(2)
             assert m.group(1) is None or int(m.group(1)) == value or callee in launchers, m.group(0)
             for k in launchers.get(callee, {callee}):
                 pairs.add((k, value))
+        for launcher in typed:
+            # the one call: from the ladder walk, with the rung's span
+            calls = re.findall(r"\b%s<T, (\w+)>\(" % launcher, text)
+            assert calls == ["SPAN"] and re.search(r"constexpr int SPAN = LzScalar<T>::kLadder\[K\]\.span;", text), (launcher, calls)
+            pairs.update((k, span) for k in launchers[launcher] for span in ladder_spans(root, src)["float"])
         for m in re.finditer(r"#define\s+(PLX_\w*CASE)\((\w+)\)((?:[^\n]*\\\n)*[^\n]*)\n", text):
             macro, body = m.group(1), m.group(3)
             named = set(re.findall(r"(\w+_kernel)<", body))

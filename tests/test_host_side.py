@@ -202,6 +202,35 @@ def test_c_abi_exports_every_declared_symbol():
             assert lib.plx_tune(key, 1) == 1, key
 
 
+def test_lanczos_step_refuses_overlap_and_misalignment():
+    """plx_lanczos_step shares the float64 step's checks: a pointer off 4-byte alignment, and a d_w with any part inside
+    rows 0..i+1 of the basis (w is read and written while those rows are read and row i + 1 is written), both
+    PLX_ERR_INVALID on host addresses: a launch that followed either would fault."""
+    lib = _native.lib()
+    who = b"plx_lanczos_step"
+    buf = (ctypes.c_float * 1024)()
+    base = (ctypes.addressof(buf) + 63) // 64 * 64               # 64-byte aligned, 900 floats of room behind it
+    at = lambda k: ctypes.c_void_p(base + 4 * k)                 # noqa: E731
+
+    def step(**kw):
+        """A valid call but for **kw: basis [2][64] at the base, w 8 floats behind it."""
+        a = dict(d_q=at(0), ld=64, d_w=at(512), n=8, i=0, d_alphas=at(600), d_betas=at(640), d_work=at(700))
+        a.update(kw)
+        return lib.plx_lanczos_step(a["d_q"], a["ld"], a["d_w"], a["n"], a["i"], a["d_alphas"], a["d_betas"], a["d_work"], None)
+
+    def refused(what):
+        err = lib.plx_last_error()
+        return who + b":" in err and what in err
+
+    # d_w at the basis start, at the last element of row i + 1, and ending inside row 0
+    for kw in (dict(d_w=at(0)), dict(d_w=at(2 * 64 - 1)), dict(d_w=at(3 * 64 + 10), i=2),
+               dict(d_q=at(4), d_w=at(0))):                      # [base, base + 8): its tail lies in row 0 at base + 4
+        assert step(**kw) == 1 and refused(b"overlaps"), kw
+    for name, k in (("d_q", 0), ("d_w", 512), ("d_alphas", 600), ("d_betas", 640), ("d_work", 700)):
+        for off in (1, 2, 3):
+            assert step(**{name: ctypes.c_void_p(base + 4 * k + off)}) == 1 and refused(b"4-byte"), (name, off)
+
+
 def test_stale_library_is_refused(monkeypatch):
     """_native.lib() checks plx_version() against the ABI its ctypes signatures describe: a libplx.so left over from
     another release (an argument added in the middle of a signature) must fail at import, not with misaligned pointers."""

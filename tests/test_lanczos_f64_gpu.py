@@ -1,6 +1,6 @@
-"""The float64 Lanczos step (simplex_gp_amd/csrc/plx_lanczos_f64.hip) on the GPU: single steps at every edge of
-plx_lanczos_shape_f64, the guard, graph replay, and the routes training.lanczos and training.PredictionCache take for a
-double model.
+"""The float64 Lanczos step (simplex_gp_amd/csrc/plx_lanczos_kernels.h with T = double) on the GPU: single steps at every
+edge of plx_lanczos_shape_f64, the guard, graph replay, and the routes training.lanczos and training.PredictionCache take
+for a double model.
 
 Bars are derived, never measured.  u = 2^-53, U2 = 2^-52 = 2 u (the unit roundoff once for each side of a comparison).  A sum
 of m terms in ANY order (lanes, waves, groups, the final tree; FMA or not) is off by at most m u sum|terms| to first order.
@@ -82,7 +82,7 @@ def span_ranges():
     return out
 
 
-# group counts whose remainder modulo 8 differs: lz64_sum_groups walks the groups in four slices, two loads per trip
+# group counts whose remainder modulo 8 differs: lz_sum_groups walks the groups in four slices, two loads per trip
 EXTRA_N = (509, 1277, 1533, 1789, 3069, 70_651, 77_819, 552_953, 1_073_000)
 
 

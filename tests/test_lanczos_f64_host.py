@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from simplex_gp_amd import _native, training
+from tests import solver64
 
 LZ64_SYMBOLS = ("plx_lanczos_work_doubles", "plx_lanczos_shape_f64", "plx_lanczos_step_f64")
 PLX_ERR_INVALID = 1
@@ -72,15 +73,19 @@ def test_work_doubles(lib):
 def test_shape(lib):
     ns = sorted(set([1, 2, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 10 ** 6, MAX_ROWS - 1, MAX_ROWS]
                     + [2 ** k + e for k in range(8, 21) for e in (-1, 0, 1)]))
-    last = 0
+    last, seen = 0, []
     for n in ns:
         rc, span, groups = shape(lib, n)
         assert rc == 0, n
+        if span not in seen:
+            seen.append(span)
         assert span * groups >= n and span * (groups - 1) < n, (n, span, groups)
         assert span >= last, (n, span, last)
         last = span
-        # static LDS of a workgroup: span doubles of w, next to red[1024] and c[256] (plx_lanczos_f64.hip)
+        # static LDS of a workgroup: span doubles of w, next to red[1024] and c[256] (plx_lanczos_kernels.h)
         assert 8 * span <= 49_152 and 8 * span + 8 * 1024 + 8 * 256 <= 65_536, (n, span)
+    # the spans the library reports over 1..2,097,152 are the double ladder of the source, the ones its dispatch instantiates
+    assert seen == solver64.ladder_spans()["double"], seen
     for n in (0, -3, MAX_ROWS + 1, 2 ** 40):
         rc, span, groups = shape(lib, n)
         assert rc == PLX_ERR_INVALID and (span, groups) == (-1, -1), n

@@ -146,7 +146,7 @@ def test_dispatch_rules():
 
 
 def test_solver_families_name_every_kernel_and_template_value():
-    """Every __global__ kernel of plx_linalg.hip, plx_pcg.hip and plx_lanczos.hip (but the two backward kernels DESIGN
+    """Every __global__ kernel of plx_linalg.hip, plx_pcg.hip and plx_lanczos_kernels.h (but the two backward kernels DESIGN
     section 10 owns) and every template value their switch statements and PLX_*_CASE lists dispatch is a family of
     solver64.FAMILIES, and FAMILIES names no kernel the sources do not have: a new kernel or value fails here until a case
     reaches it."""
@@ -159,3 +159,6 @@ def test_solver_families_name_every_kernel_and_template_value():
     assert pairs <= have, sorted(pairs - have)
     assert have <= pairs, sorted(have - pairs)
     assert len(s64.UNREACHABLE) <= 3 and set(s64.UNREACHABLE) <= set(s64.FAMILIES)
+    # the templated Lanczos source: the fp32 ladder is the table's, and no type's ladder holds a span it has no rows for
+    spans = s64.ladder_spans()
+    assert spans["float"] == list(s64.LZ_SPANS) and spans["double"] == [256, 1024, 4096]

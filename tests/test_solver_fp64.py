@@ -1,4 +1,4 @@
-"""The native solver kernels (plx_linalg.hip, plx_pcg.hip, plx_lanczos.hip) against float64, at every kernel family.
+"""The native solver kernels (plx_linalg.hip, plx_pcg.hip, plx_lanczos_kernels.h) against float64, at every kernel family.
 
 Every case calls the C ABI on fp32 data it made itself, evaluates the same expression in float64 on the CPU from the
 same fp32 values (tests/solver64.py) and judges every output entry in units of the terms it sums.  The family a call
