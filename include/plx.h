@@ -426,6 +426,68 @@ int plx_apply_backward_f64(plx_lattice *lat, const double *d_g, const double *d_
                            double *d_grad_x, double *d_grad_src /* may be NULL */, void *stream);
 
 /*
+ * The float64 position gradient of the rectangular product K(A, B) v, one side per call (callers detect it by symbol; the
+ * version string is unchanged).  With G the incoming gradient (non-zero on the out rows only) and S the right-hand side
+ * (non-zero on the source rows only), the four terms of the square gradient above split: on the source rows only
+ * s_l x_k wg_l - s_l wgx_lk lives, on the out rows only g_l x_k ws_l - g_l wsx_lk.  One call serves one side: it filters the
+ * HALF stack [ a | a (x) x ] of the rows of a to the rows of b and contracts it there against b.  (a = g on the out rows,
+ * b = src on the source rows) gives the gradient of the source rows' positions, (a = src, b = g) that of the out rows'.
+ * `lat` is built with the DERIVATIVE taps on the stacked positions rounded to float, as for plx_apply_backward_f64; d_x
+ * [n][d] is the caller's FLOAT64 position matrix of ALL stacked points.  L = nrhs, H = L (1 + d) (>= 2),
+ * stride = plx_values_stride_f64(H) (H rounded up to even).  The product block is l-major: column L + l d + k holds a_l x_k,
+ * x the row a_begin + r of d_x.
+ *   plx_backward_splat_rows_f64     d_a is [a_count][L].  d_values[m][stride] = the plx_splat_rows_f64 over rows [a_begin,
+ *                                   a_begin + a_count) of the half stack, each product element formed inside the splat as
+ *                                   ONE rounded double multiply (plain columns are copied) and accumulated as
+ *                                   fma((double)w, element, acc) in the corner order of the range's table.  Every vertex
+ *                                   row is written: a vertex the range does not touch gets 0, the padding column of an odd
+ *                                   H gets 0; there is no zero-fill pass.
+ *   plx_backward_contract_rows_f64  slice and contraction in one kernel: for row i of [b_begin, b_begin + b_count) the
+ *                                   filtered row [ wa | wax ] is formed on chip from d_values (blurred by plx_blur_f64 at
+ *                                   vd = H) with the sums of plx_slice_rows_f64 (one division by 1 + 2^-d) and contracted to
+ *                                     d_grad_x[i][k] = -2 sum_l ( (b_l x_k) wa_l - b_l wax_lk ),  k < d,
+ *                                   the sum started at 0 and taken for l ascending, the two terms in the order written,
+ *                                   b_l x_k formed first, x the row b_begin + i of d_x.  d_b is [b_count][L], d_grad_x
+ *                                   [b_count][d]; unless d_filtered is NULL, d_filtered[i][l] = wa_l, [b_count][L].
+ *   plx_apply_backward_rows_f64     the two around the blur of plx_apply_f64 at width H, on the float64 workspace that
+ *                                   plx_apply_f64 owns: m x stride doubles per plane, half of what the padded square
+ *                                   gradient needs.
+ * Rows are ALWAYS in the caller's order.  The two ranges are independent: disjoint, equal, nested or overlapping.  The
+ * range tables are the slots of the rows calls, shared with them and across precisions; nothing new is stored per range.
+ * The splat and the contraction report through plx_last_rows_f64_kernels (rows64_backward_splat_chunk_kernel /
+ * rows64_backward_splat_wide_kernel in the splat field, rows64_backward_contract_chunk_kernel /
+ * rows64_backward_contract_wide_kernel in the slice field: the chunk shape up to 64 chunks, i.e. stride <= 128, the wide
+ * shape above); the blur reports through plx_last_f64_kernels.
+ * Scope, refusals, workspace growth and the capture rule are those of plx_apply_rows_f64 and plx_apply_backward_f64 together.
+ * PLX_ERR_STATE: a lattice that is not built, a sharded or merged build, a build that replayed "reference_growth", and under
+ * stream capture a call that would have to build a range table, make the vertex row pointer or grow the workspace.
+ * PLX_ERR_INVALID: a NULL pointer other than d_filtered, nrhs < 1, a count < 1, a range outside [0, n), a pointer off 8-byte
+ * alignment, d_values off 16-byte alignment, an output that aliases an input or the other output, and stride > 2048 (the
+ * wide contraction keeps four rows of `stride` doubles in the 64 KiB of LDS of a workgroup, the limit of
+ * plx_apply_backward_f64).  PLX_ERR_TOO_LARGE: m * stride, a_count * stride or b_count * stride at or over 2^31.  Every
+ * argument is checked before any GPU work: a refused call writes nothing.  From the second call of a (range pair, width)
+ * on, a call neither allocates nor synchronises (plx_device_bytes does not move) and is graph-capturable.  No float
+ * atomics, every output element written by exactly one thread: two calls with the same arguments are bit-equal.
+ * Two contracts.  (i) Bits, AS VALUES (-0.0 counted equal to +0.0): plx_backward_splat_rows_f64 equals plx_splat_rows_f64
+ * of the explicit half stack formed in double with one multiply per product element, in all `stride` columns; d_filtered
+ * equals columns [0, L) of plx_apply_rows_f64 of that half stack, and rows [b_begin, b_begin + b_count) of the d_grad_src
+ * of plx_apply_backward_f64 on the zero-padded n-row matrices, for every pair of ranges; the staged calls (splat,
+ * plx_blur_f64 at vd = H, contract) give the bits of plx_apply_backward_rows_f64.  (ii) Bar: every entry of d_grad_x is
+ * within 2 (k + 2 (L + 1)) 2^-52 of the size of the terms it sums (k: the depth of the fp64 product's sums,
+ * tests/test_backward_f64_gpu.py) of the contraction of a float64 filter of the half stack, and exactly 0 where no term
+ * reaches it.  The two one-sided results added into [n][d] agree with plx_apply_backward_f64 of the padded problem to
+ * rounding; bit equality with it is not promised.
+ */
+int plx_backward_splat_rows_f64(plx_lattice *lat, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_x,
+                                int nrhs, double *d_values, void *stream);
+int plx_backward_contract_rows_f64(plx_lattice *lat, const double *d_values, const double *d_b, int64_t b_begin,
+                                   int64_t b_count, const double *d_x, int nrhs, double *d_grad_x,
+                                   double *d_filtered /* may be NULL */, void *stream);
+int plx_apply_backward_rows_f64(plx_lattice *lat, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_b,
+                                int64_t b_begin, int64_t b_count, const double *d_x, int nrhs, double *d_grad_x,
+                                double *d_filtered /* may be NULL */, void *stream);
+
+/*
  * The reference's one-shot call (cpp:6-10 -> h:259-340): build a lattice for
  * d_ref, apply it to d_src, leave nothing behind.  `scratch` may be NULL or a
  * lattice object whose buffers are reused (avoids hipMalloc in steady state; it

@@ -732,10 +732,11 @@ int plx_last_rows_f64_kernels(const plx_lattice *L, char *buf, int cap)
 // ---- the float64 position gradient (kernels: plx_backward_f64.hip; blur: plx_f64.hip) ------------------------------------
 
 // Everything a float64 position-gradient call checks before any GPU work.  in[0..n_in): the input buffers; out[0..n_out): the
-// output buffers, of which only a trailing d_grad_src may be NULL.  What needs no lattice comes first; then check_f64 on
-// the 2 nrhs (1 + d) columns of the stack, which are whole 16-byte rows (the count is even).
-static int check_backward_f64(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
-                              bool last_out_optional, int nrhs, const char *who)
+// output buffers, of which only a trailing d_grad_src may be NULL.  What needs no lattice comes first (check_backward_ptrs,
+// shared with the row-range form below); then check_f64 on the 2 nrhs (1 + d) columns of the stack, which are whole 16-byte
+// rows (the count is even).
+static int check_backward_ptrs(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
+                               bool last_out_optional, int nrhs, const char *who)
 {
     if (!L) { set_error("%s: NULL lattice", who); return PLX_ERR_INVALID; }
     for (int i = 0; i < n_in; ++i)
@@ -752,6 +753,13 @@ static int check_backward_f64(const plx_lattice *L, const void *const *in, int n
         for (int q = 0; q < o; ++q) alias |= out[o] == out[q];
         if (alias) { set_error("%s: an output buffer must not alias an input or another output", who); return PLX_ERR_INVALID; }
     }
+    return PLX_OK;
+}
+
+static int check_backward_f64(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
+                              bool last_out_optional, int nrhs, const char *who)
+{
+    PLX_TRY(check_backward_ptrs(L, in, n_in, out, n_out, last_out_optional, nrhs, who));
     const int64_t cols = 2ll * nrhs * (1 + (L->built ? L->d : 0));
     if (L->built && cols > kBackwardF64MaxCols) {
         set_error("%s: nrhs = %d, d = %d is %lld stacked columns; the on-chip row of the contraction holds up to %d", who, nrhs,
@@ -799,6 +807,76 @@ int plx_apply_backward_f64(plx_lattice *L, const double *d_g, const double *d_sr
     PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), 2 * nrhs * (1 + L->d), &in_b, s));
     return backward_contract_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), d_g, d_src, d_x, nrhs,
                                       d_grad_x, d_grad_src, s);
+}
+
+// ---- the float64 position gradient of the rectangular product, one side per call (kernels: plx_rows_backward_f64.hip) ----
+
+// Everything a one-sided call checks before any GPU work: the pointer checks of check_backward_f64 and the counts, which
+// need no lattice, first; then the built lattice, the column limit on the row stride, the ranges, the build and the sizes.
+static int check_backward_rows_f64(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
+                                   bool last_out_optional, int nrhs, const int64_t (*ranges)[2], int n_ranges, const char *who)
+{
+    PLX_TRY(check_backward_ptrs(L, in, n_in, out, n_out, last_out_optional, nrhs, who));
+    for (int r = 0; r < n_ranges; ++r)
+        if (ranges[r][1] < 1) { set_error("%s: a row count of %lld must be positive", who, (long long)ranges[r][1]); return PLX_ERR_INVALID; }
+    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
+    const int64_t cols = (int64_t)nrhs * (1 + L->d), stride = (cols + 1) & ~1ll;
+    if (stride > kBackwardF64MaxCols) {
+        set_error("%s: nrhs = %d, d = %d is a row of %lld doubles; the on-chip row of the contraction holds up to %d", who, nrhs,
+                  L->d, (long long)stride, kBackwardF64MaxCols);
+        return PLX_ERR_INVALID;
+    }
+    for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_range(L, ranges[r][0], ranges[r][1], who));
+    PLX_TRY(check_plain_build(L, "the float64 row-range gradient is", who));
+    for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_size(L, (int)stride, ranges[r][1], "rows", who));
+    return PLX_OK;
+}
+
+int plx_backward_splat_rows_f64(plx_lattice *L, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_x, int nrhs,
+                                double *d_values, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_a, d_x}, *out[] = {d_values};
+    const int64_t ranges[][2] = {{a_begin, a_count}};
+    PLX_TRY(check_backward_rows_f64(L, in, 2, out, 1, false, nrhs, ranges, 1, "plx_backward_splat_rows_f64"));
+    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_splat_rows_f64"));
+    DeviceGuard g(L->device);
+    return backward_splat_rows_f64_impl(L, d_a, a_begin, a_count, d_x, nrhs, d_values, (hipStream_t)stream);
+}
+
+int plx_backward_contract_rows_f64(plx_lattice *L, const double *d_values, const double *d_b, int64_t b_begin, int64_t b_count,
+                                   const double *d_x, int nrhs, double *d_grad_x, double *d_filtered, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_values, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
+    const int64_t ranges[][2] = {{b_begin, b_count}};
+    PLX_TRY(check_backward_rows_f64(L, in, 3, out, 2, true, nrhs, ranges, 1, "plx_backward_contract_rows_f64"));
+    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_contract_rows_f64"));
+    DeviceGuard g(L->device);
+    return backward_contract_rows_f64_impl(L, d_values, d_b, b_begin, b_count, d_x, nrhs, d_grad_x, d_filtered,
+                                           (hipStream_t)stream);
+}
+
+int plx_apply_backward_rows_f64(plx_lattice *L, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_b,
+                                int64_t b_begin, int64_t b_count, const double *d_x, int nrhs, double *d_grad_x,
+                                double *d_filtered, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_a, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
+    const int64_t ranges[][2] = {{a_begin, a_count}, {b_begin, b_count}};
+    PLX_TRY(check_backward_rows_f64(L, in, 3, out, 2, true, nrhs, ranges, 2, "plx_apply_backward_rows_f64"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int H = nrhs * (1 + L->d);
+    const size_t bytes = (size_t)L->m * values_stride_f64(H) * 8;
+    PLX_TRY(ensure(L->val64_a, bytes));      // the workspace of plx_apply_f64
+    PLX_TRY(ensure(L->val64_b, bytes));
+    PLX_TRY(backward_rows_f64_tables(L, a_begin, a_count, b_begin, b_count, s));
+    PLX_TRY(backward_splat_rows_f64_impl(L, d_a, a_begin, a_count, d_x, nrhs, L->val64_a.as<double>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), H, &in_b, s));
+    return backward_contract_rows_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), d_b, b_begin, b_count,
+                                           d_x, nrhs, d_grad_x, d_filtered, s);
 }
 
 int plx_apply_backward(plx_lattice *L, const float *d_g, const float *d_src, const float *d_ref, int nrhs,

@@ -31,49 +31,8 @@
 
 namespace plx {
 
-// One column of the stack: where its factor a comes from, and k >= 0 for a product column a * x[k] (-1: the plain column).
-struct StackCol64 {
-    const double *a;
-    int l, k;
-};
-
-__device__ __forceinline__ StackCol64 stack_col64(int c, const double *__restrict__ g, const double *__restrict__ src, int L, int d)
-{
-    const int h = L * (1 + d);
-    StackCol64 s;
-    s.a = c < h ? g : src;
-    if (c >= h) c -= h;
-    if (c < L) {
-        s.l = c;
-        s.k = -1;
-    } else {
-        c -= L;
-        s.l = c / d;
-        s.k = c - s.l * d;
-    }
-    return s;
-}
-
-__device__ __forceinline__ double stack_elem64(const StackCol64 &s, const double *__restrict__ x, size_t row, int L, int d)
-{
-    const double a = s.a[row * L + s.l];
-    return s.k < 0 ? a : a * x[row * d + s.k];
-}
-
-// f64_vertex_sum over chunk ch of the stack rows: the same weights, the same corner order, the same fma
-__device__ __forceinline__ double2 stack_vertex_sum64(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
-                                                      const double *__restrict__ g, const double *__restrict__ src,
-                                                      const double *__restrict__ x, int L, int d, int ch)
-{
-    const StackCol64 c0 = stack_col64(2 * ch, g, src, L, d), c1 = stack_col64(2 * ch + 1, g, src, L, d);
-    double2 acc = VecOps<double2>::zero();
-    for (int j = j0; j < j1; ++j) {
-        const size_t r = (size_t)(row[j] & 0x7FFFFFFF);
-        VecOps<double2>::fma(acc, (double)w[j], make_double2(stack_elem64(c0, x, r, L, d), stack_elem64(c1, x, r, L, d)));
-    }
-    return acc;
-}
-
+// (the stack element and its vertex sum -- StackCol64, stack_col64, stack_elem64, stack_vertex_sum64 -- are in plx_kernels.h,
+// shared with plx_rows_backward_f64.hip)
 __global__ __launch_bounds__(kBlock) void f64_backward_splat_chunk_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
                                                                           const float *__restrict__ w, const double *__restrict__ g,
                                                                           const double *__restrict__ src, const double *__restrict__ x,
@@ -100,41 +59,7 @@ __global__ __launch_bounds__(kBlock) void f64_backward_splat_wide_kernel(const i
 }
 
 // ---- slice + contraction -------------------------------------------------------------------------------------------
-// The corners of point p, read once per lane.  D1 > 0: d + 1 compiled in; 0: nothing is kept, the run-time form reads them.
-template <int D1> struct Corners64 {
-    int v[D1];
-    double w[D1];
-    __device__ __forceinline__ void load(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p)
-    {
-#pragma unroll
-        for (int r = 0; r < D1; ++r) v[r] = evid[(size_t)r * n + p];
-#pragma unroll
-        for (int r = 0; r < D1; ++r) w[r] = (double)ew[(size_t)r * n + p];
-    }
-};
-template <> struct Corners64<0> {
-    __device__ __forceinline__ void load(const int *, const float *, int, int) {}
-};
-
-// chunk ch of the filtered row of point p: the sum of f64_slice_chunk_kernel (all gathers, then the ordered sum, one division)
-template <int D1>
-__device__ __forceinline__ double2 filtered_chunk64(const Corners64<D1> &c, const int *__restrict__ evid, const float *__restrict__ ew,
-                                                    int n, int p, int d1, const double2 *__restrict__ values, int nch, int ch,
-                                                    double denom)
-{
-    if constexpr (D1 > 0) {
-        double2 gath[D1];
-#pragma unroll
-        for (int r = 0; r < D1; ++r) gath[r] = values[(size_t)c.v[r] * nch + ch];
-        double2 acc = VecOps<double2>::zero();
-#pragma unroll
-        for (int r = 0; r < D1; ++r) VecOps<double2>::fma(acc, c.w[r], gath[r]);
-        return make_double2(acc.x / denom, acc.y / denom);
-    } else {
-        return f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom);
-    }
-}
-
+// (the corners of a point and the chunk of its filtered row -- Corners64, filtered_chunk64 -- are in plx_kernels.h)
 // f: the point's filtered row [ wg | wgx | ws | wsx ] of C doubles in LDS.  Lane `lane` of `lanes` takes k = lane, lane +
 // lanes, ... and then l likewise: every output element has one writer.
 __device__ __forceinline__ void contract_row64(const double *f, int lane, int lanes, size_t row, const double *__restrict__ g,

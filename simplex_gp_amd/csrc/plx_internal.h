@@ -409,6 +409,16 @@ int backward_splat_f64_impl(plx_lattice *L, const double *d_g, const double *d_s
                             double *d_values, hipStream_t stream);
 int backward_contract_f64_impl(plx_lattice *L, const double *d_values, const double *d_g, const double *d_src,
                                const double *d_x, int nrhs, double *d_grad_x, double *d_grad_src, hipStream_t stream);
+// plx_rows_backward_f64.hip: the one-sided float64 position gradient of the rectangular product -- the splat of the half
+// stack [ a | a (x) x ] (nrhs (1 + d) columns) over the rows of a, and the slice with the contraction against b fused over
+// the rows of b (arguments checked by the entry points); d_x is [n][d], all stacked points.  backward_rows_f64_tables:
+// both range tables of a call before its first launch.  The column limit is kBackwardF64MaxCols on the row stride.
+int backward_rows_f64_tables(plx_lattice *L, int64_t a_begin, int64_t a_count, int64_t b_begin, int64_t b_count,
+                             hipStream_t stream);
+int backward_splat_rows_f64_impl(plx_lattice *L, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_x, int nrhs,
+                                 double *d_values, hipStream_t stream);
+int backward_contract_rows_f64_impl(plx_lattice *L, const double *d_values, const double *d_b, int64_t b_begin, int64_t b_count,
+                                    const double *d_x, int nrhs, double *d_grad_x, double *d_filtered, hipStream_t stream);
 // plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
 int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,

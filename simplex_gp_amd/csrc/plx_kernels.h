@@ -1,6 +1,6 @@
 // plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
 // plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip,
-// plx_rows_f64.hip).  Not part of the C ABI.
+// plx_rows_f64.hip, plx_backward_f64.hip, plx_rows_backward_f64.hip).  Not part of the C ABI.
 //
 // Reference: cpp/permutohedral.h ("h") splat value accumulation h:478-479,
 // blur h:513-572, slice h:497-510.  The reference's CUDA path does the splat
@@ -131,6 +131,86 @@ __device__ __forceinline__ double2 f64_point_sum(const int *__restrict__ evid, c
     for (int r = 0; r < d1; ++r)
         VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)evid[(size_t)r * n + p] * nch + ch]);
     return make_double2(acc.x / denom, acc.y / denom);
+}
+
+// ---- the float64 position gradients (plx_backward_f64.hip, plx_rows_backward_f64.hip): the stack formed inside the splat
+// and the filtered row formed inside the slice, shared so that both files give the same bits ----
+// One column of the stack: where its factor a comes from, and k >= 0 for a product column a * x[k] (-1: the plain column).
+struct StackCol64 {
+    const double *a;
+    int l, k;
+};
+
+__device__ __forceinline__ StackCol64 stack_col64(int c, const double *__restrict__ g, const double *__restrict__ src, int L, int d)
+{
+    const int h = L * (1 + d);
+    StackCol64 s;
+    s.a = c < h ? g : src;
+    if (c >= h) c -= h;
+    if (c < L) {
+        s.l = c;
+        s.k = -1;
+    } else {
+        c -= L;
+        s.l = c / d;
+        s.k = c - s.l * d;
+    }
+    return s;
+}
+
+__device__ __forceinline__ double stack_elem64(const StackCol64 &s, const double *__restrict__ x, size_t row, int L, int d)
+{
+    const double a = s.a[row * L + s.l];
+    return s.k < 0 ? a : a * x[row * d + s.k];
+}
+
+// f64_vertex_sum over chunk ch of the stack rows: the same weights, the same corner order, the same fma
+__device__ __forceinline__ double2 stack_vertex_sum64(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
+                                                      const double *__restrict__ g, const double *__restrict__ src,
+                                                      const double *__restrict__ x, int L, int d, int ch)
+{
+    const StackCol64 c0 = stack_col64(2 * ch, g, src, L, d), c1 = stack_col64(2 * ch + 1, g, src, L, d);
+    double2 acc = VecOps<double2>::zero();
+    for (int j = j0; j < j1; ++j) {
+        const size_t r = (size_t)(row[j] & 0x7FFFFFFF);
+        VecOps<double2>::fma(acc, (double)w[j], make_double2(stack_elem64(c0, x, r, L, d), stack_elem64(c1, x, r, L, d)));
+    }
+    return acc;
+}
+
+// The corners of point p, read once per lane.  D1 > 0: d + 1 compiled in; 0: nothing is kept, the run-time form reads them.
+template <int D1> struct Corners64 {
+    int v[D1];
+    double w[D1];
+    __device__ __forceinline__ void load(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p)
+    {
+#pragma unroll
+        for (int r = 0; r < D1; ++r) v[r] = evid[(size_t)r * n + p];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) w[r] = (double)ew[(size_t)r * n + p];
+    }
+};
+template <> struct Corners64<0> {
+    __device__ __forceinline__ void load(const int *, const float *, int, int) {}
+};
+
+// chunk ch of the filtered row of point p: the sum of f64_slice_chunk_kernel (all gathers, then the ordered sum, one division)
+template <int D1>
+__device__ __forceinline__ double2 filtered_chunk64(const Corners64<D1> &c, const int *__restrict__ evid, const float *__restrict__ ew,
+                                                    int n, int p, int d1, const double2 *__restrict__ values, int nch, int ch,
+                                                    double denom)
+{
+    if constexpr (D1 > 0) {
+        double2 gath[D1];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) gath[r] = values[(size_t)c.v[r] * nch + ch];
+        double2 acc = VecOps<double2>::zero();
+#pragma unroll
+        for (int r = 0; r < D1; ++r) VecOps<double2>::fma(acc, c.w[r], gath[r]);
+        return make_double2(acc.x / denom, acc.y / denom);
+    } else {
+        return f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom);
+    }
 }
 
 constexpr int kF64ChunkMax = 64;      // chunks one lane group can cover: a group never spans two waves

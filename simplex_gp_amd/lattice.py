@@ -634,6 +634,46 @@ class Lattice:
         nv.check(rc, "plx_apply_backward_f64")
         return grad_ref, grad_src
 
+    BACKWARD_ROWS_F64_MAX_STRIDE = 2048      # kBackwardF64MaxCols on the row stride of the half stack
+
+    @staticmethod
+    def backward_rows_f64_ok(nrhs, d):
+        """True when plx_apply_backward_rows_f64 covers this shape: nrhs >= 1, d >= 1 and the row of the half stack --
+        nrhs*(1+d) doubles rounded up to even -- within 2048."""
+        return nrhs >= 1 and d >= 1 and (nrhs * (1 + d) + 1) // 2 * 2 <= Lattice.BACKWARD_ROWS_F64_MAX_STRIDE
+
+    def apply_backward_rows(self, a, a_begin, b, b_begin, x, want_filtered=True):
+        """One side of the position gradient of the rectangular product, for a lattice built with the DERIVATIVE taps on
+        the stacked positions `x` [n, d] rounded to float32 (plx_apply_backward_rows_f64): the half stack [a | a (x) x] of
+        rows [a_begin, a_begin + len(a)) is filtered to rows [b_begin, b_begin + len(b)) and contracted there against b.
+        Returns (grad_x [len(b), d], filtered [len(b), nrhs] or None); filtered is the derivative-tap filter of `a` on the
+        rows of b.  (a = grad_out on the out rows, b = src on the source rows) is the gradient of the source rows'
+        positions, (a = src, b = grad_out) that of the out rows'.  float64 CUDA tensors only: there is no fp32 form."""
+        for t, name in ((a, "a"), (b, "b"), (x, "x")):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch.Tensor")
+        if {a.dtype, b.dtype, x.dtype} != {torch.float64}:
+            raise TypeError("apply_backward_rows has no fp32 form: a, b and x must all be float64, got "
+                            f"{a.dtype}, {b.dtype} and {x.dtype}")
+        for t, name in ((a, "a"), (b, "b"), (x, "x")):
+            _check_f32_cuda(t, name, f64_ok=True)
+        a, b, x = a.contiguous(), b.contiguous(), self._src(x, self.n, f64_ok=True)
+        ab, ac = self._rows(a_begin, a.shape[0])
+        bb, bc = self._rows(b_begin, b.shape[0])
+        if a.shape[1] != b.shape[1] or x.shape[1] != self.d:
+            raise ValueError(f"Incompatible shapes {tuple(a.shape)}, {tuple(b.shape)}, {tuple(x.shape)}")
+        nrhs = a.shape[1]
+        grad_x = torch.empty((bc, self.d), dtype=torch.float64, device=self.device)
+        filtered = torch.empty((bc, nrhs), dtype=torch.float64, device=self.device) if want_filtered else None
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_apply_backward_rows_f64(self._h, ctypes.c_void_p(a.data_ptr()), ab, ac,
+                                                      ctypes.c_void_p(b.data_ptr()), bb, bc, ctypes.c_void_p(x.data_ptr()),
+                                                      nrhs, ctypes.c_void_p(grad_x.data_ptr()),
+                                                      ctypes.c_void_p(filtered.data_ptr()) if want_filtered else None,
+                                                      _stream_ptr(self.device))
+        nv.check(rc, "plx_apply_backward_rows_f64")
+        return grad_x, filtered
+
     # -- introspection (parity tests) --------------------------------------
     def export(self, which):
         L = nv.lib()

@@ -324,31 +324,66 @@ class LatticeRowsProduct(Function):
     """out = K[out rows, src rows] @ source on the lattice of `positions` (the stacked points of a rectangular operator):
     only the rows that carry a right-hand side are splatted, only the wanted rows are sliced (plx_apply_rows).  The
     gradient with respect to `source` is the transposed product on the same lattice, ranges swapped (K is treated as
-    symmetric, py:110-111).  No position gradient: RectangularLazyLattice keeps the padded path for that."""
+    symmetric, py:110-111).
+
+    Position gradient: only with the discretised kernel as the trailing argument (RectangularLazyLattice passes it where
+    native_rows_grad_f64 sends a float64 product here); without it there is none and RectangularLazyLattice keeps the
+    padded path for that.  It is py:113-123 split by sides -- the incoming gradient lives on the out rows only, the
+    right-hand side on the source rows only -- into two one-sided calls on the derivative-tap lattice of the stacked
+    positions (Lattice.apply_backward_rows), added into one zero [n, d] tensor; grad_source is then
+    the derivative-tap filter of the incoming gradient, as LatticeFilterGeneral.backward returns it (py:123)."""
 
     @staticmethod
-    def forward(ctx, source, positions, coeffs, lat, src_begin, out_begin, out_count):
-        ctx.positions, ctx.coeffs = positions, coeffs
+    def forward(ctx, source, positions, coeffs, lat, src_begin, out_begin, out_count, kernel_fn=None):
+        ctx.coeffs = coeffs
         ctx.ranges = (int(src_begin), int(source.shape[0]), int(out_begin), int(out_count))
+        ctx.deriv_coeffs = None
+        if kernel_fn is not None and ctx.needs_input_grad[1]:
+            ctx.deriv_coeffs = kernel_fn.get_deriv_coeffs()
+            ctx.save_for_backward(source, positions)
+        else:
+            ctx.positions = positions
         return lat.apply_rows(source, src_begin, out_begin, out_count)
 
     @staticmethod
     def backward(ctx, grad_output):
-        grad_source = None
-        if ctx.needs_input_grad[0]:
-            sb, sc, ob, oc = ctx.ranges
+        grad_source = grad_positions = None
+        sb, sc, ob, oc = ctx.ranges
+        if ctx.deriv_coeffs is not None:
+            with torch.no_grad():
+                source, positions = ctx.saved_tensors
+                g = grad_output.contiguous()
+                lat = _cache.get(positions, ctx.deriv_coeffs)     # the derivative-tap lattice of the stacked positions
+                # a = g on the out rows, b = source on the source rows: the source rows' positions (and wg on them)
+                grad_in, grad_source = lat.apply_backward_rows(g, ob, source, sb, positions,
+                                                               want_filtered=ctx.needs_input_grad[0])
+                # a = source on the source rows, b = g on the out rows: the out rows' positions
+                grad_out, _ = lat.apply_backward_rows(source, sb, g, ob, positions, want_filtered=False)
+                grad_positions = torch.zeros_like(positions)
+                grad_positions[sb:sb + sc] += grad_in
+                grad_positions[ob:ob + oc] += grad_out
+        elif ctx.needs_input_grad[0]:
             with torch.no_grad():
                 lat = _cache.get(ctx.positions, ctx.coeffs)       # the forward's lattice (rebuilt if it was evicted since)
                 grad_source = lat.apply_rows(grad_output.contiguous(), ob, sb, sc)
-        return grad_source, None, None, None, None, None, None
+        return grad_source, grad_positions, None, None, None, None, None, None
 
 
-def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1, f64=False):
+def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1, f64=False,
+               grad_f64=False):
     """Whether K(xin, xout) @ V goes through the native row-range product: a CUDA fp32 2-D right-hand side -- or, with
     f64=True (RectangularLazyLattice.native_rows_f64), a float64 one --, no test hook / foreign filter installed
     (LatticeFilterGeneral.method), no gradient wanted for the positions, the route switched on
     (RectangularLazyLattice.native_rows) and, where the caller says how many columns V has, at least `min_columns` of them
-    (RectangularLazyLattice.native_min_columns).  Everything else takes the padded square filter."""
+    (RectangularLazyLattice.native_min_columns).  Everything else takes the padded square filter.
+
+    grad_f64=True (RectangularLazyLattice.native_rows_grad_f64) asks the other question: whether a product whose positions
+    DO want a gradient goes through the native route with its native float64 position gradient.  That admits only a CUDA
+    float64 2-D right-hand side with requires_grad set, no hook, the route switched on; the width gate does not apply
+    (it was measured for the fp32 forward)."""
+    if grad_f64:
+        return bool(enabled and device_type == "cuda" and dtype == torch.float64 and dim == 2 and hook is None
+                    and requires_grad)
     dtype_ok = dtype == torch.float32 or (bool(f64) and dtype == torch.float64)
     return bool(enabled and device_type == "cuda" and dtype_ok and dim == 2 and hook is None
                 and not requires_grad and (columns is None or columns >= min_columns))
@@ -400,11 +435,20 @@ class RectangularLazyLattice(LazyTensor):
     native_rows_f64: whether a float64 V takes the native route too (plx_apply_rows_f64; the same width gate).  The
     native and the padded float64 products are equal as values, so the switch changes time and
     memory only.  It is off until the native product has been measured no slower than the padded one at 101 columns in
-    both directions (profiles/rows_f64_measured.md: not measured yet)."""
+    both directions (profiles/rows_f64_measured.md: not measured yet).
+
+    native_rows_grad_f64: whether a float64 2-D V whose positions WANT a gradient takes the native route as well, with the
+    position gradient as two one-sided native calls of half the padded width (LatticeRowsProduct)
+    instead of one padded square gradient.  Both lattices (the kernel's taps and the derivative taps, on the stacked
+    points) must accept rows and Lattice.backward_rows_f64_ok must hold; native_min_columns does not apply (it was
+    measured for the fp32 forward).  The two routes agree to rounding.  Off until the native route has been measured no
+    slower than the padded one at every shape of tools/rows_backward_f64_time.py
+    (profiles/rows_backward_f64_measured.md)."""
 
     native_rows = True
     native_min_columns = 101
     native_rows_f64 = False
+    native_rows_grad_f64 = False
 
     def __init__(self, xin, xout, dkernel=None):
         super().__init__(xin, xout, dkernel=dkernel)
@@ -427,6 +471,19 @@ class RectangularLazyLattice(LazyTensor):
                 nb_out = base.xout.shape[-2]
                 src_begin, out_begin = (nb_out, 0) if swapped else (0, nb_out)
                 return LatticeRowsProduct.apply(V, stacked, coeffs, lat, src_begin, out_begin, n_in)
+        elif (type(self).native_rows_grad_f64
+              and rows_route(V.device.type, V.dtype, V.dim(), LatticeFilterGeneral.method, wants_grad, type(self).native_rows,
+                             grad_f64=True)
+              and Lattice.backward_rows_f64_ok(V.shape[-1], self.xin.shape[-1])):
+            base, swapped = self.__dict__.get("_rows_base", (self, False))
+            stacked = base._stacked_points()                       # the concatenation WITH its gradient history
+            coeffs = self.dkernel.get_coeffs()
+            lat = _cache.get(stacked, coeffs)
+            dlat = _cache.get(stacked, self.dkernel.get_deriv_coeffs())
+            if lat.accepts_rows() and dlat.accepts_rows():
+                nb_out = base.xout.shape[-2]
+                src_begin, out_begin = (nb_out, 0) if swapped else (0, nb_out)
+                return LatticeRowsProduct.apply(V, stacked, coeffs, lat, src_begin, out_begin, n_in, self.dkernel)
         stacked_rhs = torch.nn.functional.pad(V, (0, 0, 0, n_in))          # zero rows for the points of xin
         return _lattice_matvec(stacked_rhs, self._stacked_points(), self.dkernel)[..., n_out:, :]
 
