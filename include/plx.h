@@ -488,6 +488,62 @@ int plx_apply_backward_rows_f64(plx_lattice *lat, const double *d_a, int64_t a_b
                                 double *d_filtered /* may be NULL */, void *stream);
 
 /*
+ * The fp32 position gradient of the rectangular product K(A, B) v, one side per call (callers detect it by symbol; the
+ * version string is unchanged): the split of plx_apply_backward_rows_f64 above on buffers of floats.  One call filters the
+ * HALF stack [ a | a (x) x ] of the rows of a to the rows of b and contracts it there against b.  (a = g on the out rows,
+ * b = src on the source rows) gives the gradient of the source rows' positions, (a = src, b = g) that of the out rows'.
+ * `lat` is built with the DERIVATIVE taps on d_x, the [n][d] positions of ALL stacked points.  L = nrhs, H = L (1 + d)
+ * (>= 2, so there is no single-column shape), stride = plx_values_stride(H) (H rounded up to 4: value rows are whole
+ * float4 chunks).  Column c of the half stack: c < L is the plain column l = c, else the product column
+ * (l, k) = divmod(c - L, d), l-major (column L + l d + k holds a_l x_k, x the row a_begin + r of d_x); the padding columns
+ * H <= c < stride are 0.
+ *   plx_backward_splat_rows     d_a is [a_count][L].  d_values[m][stride] = the plx_splat_rows over rows [a_begin,
+ *                               a_begin + a_count) of the half stack, each product element formed inside the splat as ONE
+ *                               rounded float multiply (plain columns are copied) and accumulated as acc += w * element in
+ *                               the corner order of the range's table.  Every vertex row is written: a vertex the range
+ *                               does not touch gets 0; there is no zero-fill pass.
+ *   plx_backward_contract_rows  slice and contraction in one kernel: for row i of [b_begin, b_begin + b_count) the filtered
+ *                               row [ wa | wax ] is formed on chip from d_values (blurred by plx_blur at vd = H) with the
+ *                               sums of plx_slice_rows (every term multiplied by the rounded 1 / (1 + 2^-d)) and contracted to
+ *                                 d_grad_x[i][k] = -2 sum_l ( (b_l x_k) wa_l - b_l wax_lk ),  k < d,
+ *                               the sum started at 0 and taken for l ascending, the two terms in the order written, b_l x_k
+ *                               formed first, x the row b_begin + i of d_x.  d_b is [b_count][L], d_grad_x [b_count][d];
+ *                               unless d_filtered is NULL, d_filtered[i][l] = wa_l, [b_count][L].
+ *   plx_apply_backward_rows     the two around the blur of plx_apply at vd = H, on the fp32 workspace of plx_apply_rows:
+ *                               m x stride floats per plane, half of what the padded square gradient needs.
+ * Rows are ALWAYS in the caller's order.  The two ranges are independent: disjoint, equal, nested or overlapping.  The
+ * range tables are the slots of the rows calls, shared with them and across precisions; nothing new is stored per range.
+ * The splat and the contraction report through plx_last_rows_kernels (rows_backward_splat_chunk_kernel /
+ * rows_backward_splat_wide_kernel in the splat field, rows_backward_contract_chunk_kernel /
+ * rows_backward_contract_wide_kernel in the slice field: the chunk shape up to 64 chunks, i.e. stride <= 256, the wide shape
+ * above); the blur reports through plx_last_kernels.
+ * PLX_ERR_STATE: a lattice that is not built, a sharded or merged build, a build that replayed "reference_growth", and under
+ * stream capture a call that would have to build a range table or grow the workspace.  PLX_ERR_INVALID: a NULL pointer other
+ * than d_filtered, nrhs < 1, a count < 1, a range outside [0, n), a pointer off 4-byte alignment, d_values off 16-byte
+ * alignment, an output that aliases an input or the other output, and stride > 4096 (the wide contraction keeps four rows of
+ * `stride` floats in the 64 KiB of LDS of a workgroup).  PLX_ERR_TOO_LARGE: m * stride, a_count * stride or b_count * stride
+ * at or over 2^31.  Every argument is checked before any GPU work: a refused call writes nothing.  From the second call of a
+ * (range pair, width) on, a call neither allocates nor synchronises (plx_device_bytes does not move) and is
+ * graph-capturable.  No atomics, every output element written by exactly one thread: two calls with the same arguments are
+ * bit-equal.
+ * Two contracts.  (i) Bits, AS VALUES (-0.0 counted equal to +0.0): plx_backward_splat_rows equals plx_splat_rows of the
+ * explicit half stack formed in float with one multiply per product element, in all `stride` columns; d_filtered equals
+ * columns [0, L) of plx_apply_rows of that half stack, for every pair of ranges; the staged calls (splat, plx_blur at
+ * vd = H, contract) give the bits of plx_apply_backward_rows.  (ii) Bar: every entry of d_grad_x is within
+ * (k32 + 2 (L + 1)) 2^-23 of the size of the terms it sums (k32: the fp32 roundings along the deepest path of the product,
+ * DESIGN.md section 22) of the contraction of a float64 filter of the half stack, and exactly 0 where no term reaches it.
+ * The two one-sided results added into [n][d] agree with the padded square gradient to rounding; bit equality with it is not
+ * promised.
+ */
+int plx_backward_splat_rows(plx_lattice *lat, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_x,
+                            int nrhs, float *d_values, void *stream);
+int plx_backward_contract_rows(plx_lattice *lat, const float *d_values, const float *d_b, int64_t b_begin, int64_t b_count,
+                               const float *d_x, int nrhs, float *d_grad_x, float *d_filtered /* may be NULL */, void *stream);
+int plx_apply_backward_rows(plx_lattice *lat, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_b,
+                            int64_t b_begin, int64_t b_count, const float *d_x, int nrhs, float *d_grad_x,
+                            float *d_filtered /* may be NULL */, void *stream);
+
+/*
  * The reference's one-shot call (cpp:6-10 -> h:259-340): build a lattice for
  * d_ref, apply it to d_src, leave nothing behind.  `scratch` may be NULL or a
  * lattice object whose buffers are reused (avoids hipMalloc in steady state; it

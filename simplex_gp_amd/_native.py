@@ -83,6 +83,9 @@ _SIGNATURES = {
     "plx_backward_splat_rows_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "plx_backward_contract_rows_f64": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "plx_apply_backward_rows_f64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "plx_backward_splat_rows": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "plx_backward_contract_rows": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "plx_apply_backward_rows": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "plx_filter": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _f32p, _i32, _vp, _vp]),
     "plx_coldot": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "plx_coldot_work_floats": (_i64, [_i32]),
@@ -155,7 +158,8 @@ OPTIONAL_SYMBOLS = frozenset(("plx_pcg_work_doubles", "plx_pcg_gram_f64", "plx_p
                               "plx_pcg_step_direction_f64", "plx_lanczos_work_doubles", "plx_lanczos_shape_f64",
                               "plx_lanczos_step_f64", "plx_exact_work_bytes_f64", "plx_exact_splits_f64", "plx_exact_mvm_f64",
                               "plx_exact_grad_f64", "plx_backward_splat_rows_f64", "plx_backward_contract_rows_f64",
-                              "plx_apply_backward_rows_f64"))
+                              "plx_apply_backward_rows_f64", "plx_backward_splat_rows", "plx_backward_contract_rows",
+                              "plx_apply_backward_rows"))
 
 
 def declared_symbols():

@@ -735,8 +735,14 @@ int plx_last_rows_f64_kernels(const plx_lattice *L, char *buf, int cap)
 // output buffers, of which only a trailing d_grad_src may be NULL.  What needs no lattice comes first (check_backward_ptrs,
 // shared with the row-range form below); then check_f64 on the 2 nrhs (1 + d) columns of the stack, which are whole 16-byte
 // rows (the count is even).
+static int check_floats_aligned(const void *a, const char *who)
+{
+    if (((uintptr_t)a & 3) != 0) { set_error("%s: buffers of floats must be 4-byte aligned", who); return PLX_ERR_INVALID; }
+    return PLX_OK;
+}
+
 static int check_backward_ptrs(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
-                               bool last_out_optional, int nrhs, const char *who)
+                               bool last_out_optional, int nrhs, const char *who, bool f64 = true)
 {
     if (!L) { set_error("%s: NULL lattice", who); return PLX_ERR_INVALID; }
     for (int i = 0; i < n_in; ++i)
@@ -744,8 +750,8 @@ static int check_backward_ptrs(const plx_lattice *L, const void *const *in, int 
     for (int o = 0; o < n_out; ++o)
         if (!out[o] && !(last_out_optional && o == n_out - 1)) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
     if (nrhs < 1) { set_error("%s: nrhs = %d must be positive", who, nrhs); return PLX_ERR_INVALID; }
-    for (int i = 0; i < n_in; ++i) PLX_TRY(check_doubles_aligned(in[i], nullptr, who));
-    for (int o = 0; o < n_out; ++o) PLX_TRY(check_doubles_aligned(out[o], nullptr, who));
+    for (int i = 0; i < n_in; ++i) PLX_TRY(f64 ? check_doubles_aligned(in[i], nullptr, who) : check_floats_aligned(in[i], who));
+    for (int o = 0; o < n_out; ++o) PLX_TRY(f64 ? check_doubles_aligned(out[o], nullptr, who) : check_floats_aligned(out[o], who));
     for (int o = 0; o < n_out; ++o) {
         if (!out[o]) continue;
         bool alias = false;
@@ -877,6 +883,73 @@ int plx_apply_backward_rows_f64(plx_lattice *L, const double *d_a, int64_t a_beg
     PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), H, &in_b, s));
     return backward_contract_rows_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), d_b, b_begin, b_count,
                                            d_x, nrhs, d_grad_x, d_filtered, s);
+}
+
+// ---- the fp32 position gradient of the rectangular product, one side per call (kernels: plx_rows_backward.hip) ----------
+
+// check_backward_rows_f64 for buffers of floats: the row stride is nrhs (1 + d) rounded up to 4, under kBackwardRowsMaxCols.
+static int check_backward_rows(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
+                               bool last_out_optional, int nrhs, const int64_t (*ranges)[2], int n_ranges, const char *who)
+{
+    PLX_TRY(check_backward_ptrs(L, in, n_in, out, n_out, last_out_optional, nrhs, who, false));
+    for (int r = 0; r < n_ranges; ++r)
+        if (ranges[r][1] < 1) { set_error("%s: a row count of %lld must be positive", who, (long long)ranges[r][1]); return PLX_ERR_INVALID; }
+    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
+    const int64_t cols = (int64_t)nrhs * (1 + L->d), stride = (cols + 3) & ~3ll;
+    if (stride > kBackwardRowsMaxCols) {
+        set_error("%s: nrhs = %d, d = %d is a row of %lld floats; the on-chip row of the contraction holds up to %d", who, nrhs,
+                  L->d, (long long)stride, kBackwardRowsMaxCols);
+        return PLX_ERR_INVALID;
+    }
+    for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_range(L, ranges[r][0], ranges[r][1], who));
+    PLX_TRY(check_plain_build(L, "the row-range gradient is", who));
+    for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_size(L, (int)stride, ranges[r][1], "rows", who));
+    return PLX_OK;
+}
+
+int plx_backward_splat_rows(plx_lattice *L, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_x, int nrhs,
+                            float *d_values, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_a, d_x}, *out[] = {d_values};
+    const int64_t ranges[][2] = {{a_begin, a_count}};
+    PLX_TRY(check_backward_rows(L, in, 2, out, 1, false, nrhs, ranges, 1, "plx_backward_splat_rows"));
+    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_splat_rows"));
+    DeviceGuard g(L->device);
+    return backward_splat_rows_impl(L, d_a, a_begin, a_count, d_x, nrhs, d_values, (hipStream_t)stream);
+}
+
+int plx_backward_contract_rows(plx_lattice *L, const float *d_values, const float *d_b, int64_t b_begin, int64_t b_count,
+                               const float *d_x, int nrhs, float *d_grad_x, float *d_filtered, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_values, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
+    const int64_t ranges[][2] = {{b_begin, b_count}};
+    PLX_TRY(check_backward_rows(L, in, 3, out, 2, true, nrhs, ranges, 1, "plx_backward_contract_rows"));
+    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_contract_rows"));
+    DeviceGuard g(L->device);
+    return backward_contract_rows_impl(L, d_values, d_b, b_begin, b_count, d_x, nrhs, d_grad_x, d_filtered, (hipStream_t)stream);
+}
+
+int plx_apply_backward_rows(plx_lattice *L, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_b, int64_t b_begin,
+                            int64_t b_count, const float *d_x, int nrhs, float *d_grad_x, float *d_filtered, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_a, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
+    const int64_t ranges[][2] = {{a_begin, a_count}, {b_begin, b_count}};
+    PLX_TRY(check_backward_rows(L, in, 3, out, 2, true, nrhs, ranges, 2, "plx_apply_backward_rows"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int H = nrhs * (1 + L->d);
+    const size_t bytes = (size_t)L->m * values_stride(H) * 4;
+    PLX_TRY(ensure(L->val_a, bytes));      // the workspace of plx_apply_rows
+    PLX_TRY(ensure(L->val_b, bytes));
+    PLX_TRY(backward_rows_tables(L, a_begin, a_count, b_begin, b_count, s));
+    PLX_TRY(backward_splat_rows_impl(L, d_a, a_begin, a_count, d_x, nrhs, L->val_a.as<float>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), H, &in_b, s));
+    return backward_contract_rows_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), d_b, b_begin, b_count, d_x, nrhs,
+                                       d_grad_x, d_filtered, s);
 }
 
 int plx_apply_backward(plx_lattice *L, const float *d_g, const float *d_src, const float *d_ref, int nrhs,

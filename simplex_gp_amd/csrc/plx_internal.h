@@ -419,6 +419,15 @@ int backward_splat_rows_f64_impl(plx_lattice *L, const double *d_a, int64_t a_be
                                  double *d_values, hipStream_t stream);
 int backward_contract_rows_f64_impl(plx_lattice *L, const double *d_values, const double *d_b, int64_t b_begin, int64_t b_count,
                                     const double *d_x, int nrhs, double *d_grad_x, double *d_filtered, hipStream_t stream);
+// plx_rows_backward.hip: the same one-sided gradient in fp32 on whole float4 chunks (stride = values_stride(nrhs (1 + d))),
+// over the same range tables, around blur_impl.  kBackwardRowsMaxCols: the widest row stride the on-chip row of the
+// contraction holds (4 rows of floats in 64 KiB of LDS).
+constexpr int kBackwardRowsMaxCols = 4096;
+int backward_rows_tables(plx_lattice *L, int64_t a_begin, int64_t a_count, int64_t b_begin, int64_t b_count, hipStream_t stream);
+int backward_splat_rows_impl(plx_lattice *L, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_x, int nrhs,
+                             float *d_values, hipStream_t stream);
+int backward_contract_rows_impl(plx_lattice *L, const float *d_values, const float *d_b, int64_t b_begin, int64_t b_count,
+                                const float *d_x, int nrhs, float *d_grad_x, float *d_filtered, hipStream_t stream);
 // plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
 int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,

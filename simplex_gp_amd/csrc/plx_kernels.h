@@ -1,6 +1,6 @@
 // plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
 // plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip,
-// plx_rows_f64.hip, plx_backward_f64.hip, plx_rows_backward_f64.hip).  Not part of the C ABI.
+// plx_rows_f64.hip, plx_backward_f64.hip, plx_rows_backward_f64.hip, plx_rows_backward.hip).  Not part of the C ABI.
 //
 // Reference: cpp/permutohedral.h ("h") splat value accumulation h:478-479,
 // blur h:513-572, slice h:497-510.  The reference's CUDA path does the splat
@@ -210,6 +210,60 @@ __device__ __forceinline__ double2 filtered_chunk64(const Corners64<D1> &c, cons
         return make_double2(acc.x / denom, acc.y / denom);
     } else {
         return f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom);
+    }
+}
+
+// ---- the fp32 row-range slices (plx_rows.hip, plx_rows_backward.hip): the sums both files form a filtered chunk from, so
+// that the same terms in the same order give the same bits in both ----
+// acc += (w g) rden per element: the product w g rounded, then ONE fused multiply-add.  Written with the rounding spelled out:
+// left to -ffp-contract=fast, `acc += w * g * rden` compiled to this in every kernel but the unaligned chunk slice, whose
+// first column of each chunk the vectoriser paired across corners and left unfused, so that the bits of a product depended
+// on the alignment of its output and no other kernel could promise them.
+__device__ __forceinline__ void rows_term(float4 &acc, float w, float4 g, float rden)
+{
+    acc.x = __fmaf_rn(__fmul_rn(w, g.x), rden, acc.x);
+    acc.y = __fmaf_rn(__fmul_rn(w, g.y), rden, acc.y);
+    acc.z = __fmaf_rn(__fmul_rn(w, g.z), rden, acc.z);
+    acc.w = __fmaf_rn(__fmul_rn(w, g.w), rden, acc.w);
+}
+
+// sum_r w_r values[v_r][ch] rden, in corner order, every term multiplied by the rounded reciprocal as plx_slice.hip does
+__device__ __forceinline__ float4 rows_point_sum(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
+                                                 int d1, const float4 *__restrict__ values, int nch, int ch, float rden)
+{
+    float4 acc = f4_zero();
+    for (int r = 0; r < d1; ++r) {
+        const int v = evid[(size_t)r * n + p];
+        const float wr = ew[(size_t)r * n + p];
+        const float4 g = values[(size_t)v * nch + ch];
+        rows_term(acc, wr, g, rden);
+    }
+    return acc;
+}
+
+// chunk ch of the filtered row of point p.  D1 > 0: d + 1 compiled in (all index / weight loads, then all gathers, then the
+// ordered sum); 0: the run-time form
+template <int D1>
+__device__ __forceinline__ float4 rows_filtered_chunk(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
+                                                      int d1, const float4 *__restrict__ values, int nch, int ch, float rden)
+{
+    if constexpr (D1 > 0) {
+        float4 acc = f4_zero();
+        int v[D1];
+        float wr[D1];
+        float4 g[D1];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) {
+            v[r] = evid[(size_t)r * n + p];
+            wr[r] = ew[(size_t)r * n + p];
+        }
+#pragma unroll
+        for (int r = 0; r < D1; ++r) g[r] = values[(size_t)v[r] * nch + ch];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) rows_term(acc, wr[r], g[r], rden);
+        return acc;
+    } else {
+        return rows_point_sum(evid, ew, n, p, d1, values, nch, ch, rden);
     }
 }
 

@@ -269,20 +269,7 @@ __global__ __launch_bounds__(kBlock) void rows_splat_wide_kernel(const int *__re
 }
 
 // ---- slice ---------------------------------------------------------------------------------------------------------
-// sum_r w_r values[v_r][ch] rden, in corner order, every term multiplied by the rounded reciprocal as plx_slice.hip does
-__device__ __forceinline__ float4 rows_point_sum(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
-                                                 int d1, const float4 *__restrict__ values, int nch, int ch, float rden)
-{
-    float4 acc = f4_zero();
-    for (int r = 0; r < d1; ++r) {
-        const int v = evid[(size_t)r * n + p];
-        const float wr = ew[(size_t)r * n + p];
-        const float4 g = values[(size_t)v * nch + ch];
-        acc.x += wr * g.x * rden; acc.y += wr * g.y * rden; acc.z += wr * g.z * rden; acc.w += wr * g.w * rden;
-    }
-    return acc;
-}
-
+// (rows_point_sum and rows_filtered_chunk, the sums of a filtered chunk: plx_kernels.h, shared with plx_rows_backward.hip)
 __global__ __launch_bounds__(kBlock) void rows_slice_v1_kernel(const int *__restrict__ pos, const int *__restrict__ prow,
                                                                const int *__restrict__ evid, const float *__restrict__ ew,
                                                                int n, int d1, int count, const float *__restrict__ values,
@@ -308,27 +295,7 @@ __global__ __launch_bounds__(kBlock) void rows_slice_chunk_kernel(const int *__r
     const int64_t j = t >> shift;
     const int ch = (int)(t & ((1 << shift) - 1));
     if (j >= count || ch >= nch) return;
-    const int p = pos[j];
-    float4 acc = f4_zero();
-    if constexpr (D1 > 0) {
-        int v[D1];
-        float wr[D1];
-        float4 g[D1];
-#pragma unroll
-        for (int r = 0; r < D1; ++r) {
-            v[r] = evid[(size_t)r * n + p];
-            wr[r] = ew[(size_t)r * n + p];
-        }
-#pragma unroll
-        for (int r = 0; r < D1; ++r) g[r] = values[(size_t)v[r] * nch + ch];
-#pragma unroll
-        for (int r = 0; r < D1; ++r) {
-            acc.x += wr[r] * g[r].x * rden; acc.y += wr[r] * g[r].y * rden;
-            acc.z += wr[r] * g[r].z * rden; acc.w += wr[r] * g[r].w * rden;
-        }
-    } else {
-        acc = rows_point_sum(evid, ew, n, p, d1, values, nch, ch, rden);
-    }
+    const float4 acc = rows_filtered_chunk<D1>(evid, ew, n, pos[j], d1, values, nch, ch, rden);
     rows_store_chunk<VEC>(out, (size_t)prow[j], vd, ch, acc);
 }
 

@@ -480,7 +480,8 @@ class Lattice:
 
     def rows_kernels(self):
         """Kernels launched by the last float32 splat_rows / slice_rows (or apply_rows) on this lattice: {"splat": [...],
-        "slice": [...]}; the blur of apply_rows reports through stage_kernels()."""
+        "slice": [...]}; the blur of apply_rows reports through stage_kernels().  apply_backward_rows_f32 reports here too:
+        rows_backward_splat_{chunk,wide}_kernel under "splat", rows_backward_contract_{chunk,wide}_kernel under "slice"."""
         return self._last_kernels("plx_last_rows_kernels", 256)
 
     def rows_f64_kernels(self):
@@ -672,6 +673,43 @@ class Lattice:
                                                       ctypes.c_void_p(filtered.data_ptr()) if want_filtered else None,
                                                       _stream_ptr(self.device))
         nv.check(rc, "plx_apply_backward_rows_f64")
+        return grad_x, filtered
+
+    BACKWARD_ROWS_MAX_STRIDE = 4096          # kBackwardRowsMaxCols of plx_rows_backward.hip, on the fp32 row stride
+
+    @staticmethod
+    def backward_rows_ok(nrhs, d):
+        """True when plx_apply_backward_rows covers this shape: nrhs >= 1, d >= 1 and the row of the half stack --
+        nrhs*(1+d) floats rounded up to a multiple of 4 -- within 4096."""
+        return nrhs >= 1 and d >= 1 and (nrhs * (1 + d) + 3) // 4 * 4 <= Lattice.BACKWARD_ROWS_MAX_STRIDE
+
+    def apply_backward_rows_f32(self, a, a_begin, b, b_begin, x, want_filtered=True):
+        """The fp32 form of apply_backward_rows (plx_apply_backward_rows), with its return convention: the lattice is built
+        with the DERIVATIVE taps on `x` [n, d].  float32 CUDA tensors only; the name is its own because apply_backward_rows
+        refuses every float32 tensor and does not dispatch on dtype."""
+        for t, name in ((a, "a"), (b, "b"), (x, "x")):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch.Tensor")
+        if {a.dtype, b.dtype, x.dtype} != {torch.float32}:
+            raise TypeError("apply_backward_rows_f32: a, b and x must all be float32, got "
+                            f"{a.dtype}, {b.dtype} and {x.dtype}")
+        for t, name in ((a, "a"), (b, "b"), (x, "x")):
+            _check_f32_cuda(t, name)
+        a, b, x = a.contiguous(), b.contiguous(), self._src(x, self.n)
+        ab, ac = self._rows(a_begin, a.shape[0])
+        bb, bc = self._rows(b_begin, b.shape[0])
+        if a.shape[1] != b.shape[1] or x.shape[1] != self.d:
+            raise ValueError(f"Incompatible shapes {tuple(a.shape)}, {tuple(b.shape)}, {tuple(x.shape)}")
+        nrhs = a.shape[1]
+        grad_x = torch.empty((bc, self.d), dtype=torch.float32, device=self.device)
+        filtered = torch.empty((bc, nrhs), dtype=torch.float32, device=self.device) if want_filtered else None
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_apply_backward_rows(self._h, ctypes.c_void_p(a.data_ptr()), ab, ac,
+                                                  ctypes.c_void_p(b.data_ptr()), bb, bc, ctypes.c_void_p(x.data_ptr()),
+                                                  nrhs, ctypes.c_void_p(grad_x.data_ptr()),
+                                                  ctypes.c_void_p(filtered.data_ptr()) if want_filtered else None,
+                                                  _stream_ptr(self.device))
+        nv.check(rc, "plx_apply_backward_rows")
         return grad_x, filtered
 
     # -- introspection (parity tests) --------------------------------------

@@ -327,10 +327,11 @@ class LatticeRowsProduct(Function):
     symmetric, py:110-111).
 
     Position gradient: only with the discretised kernel as the trailing argument (RectangularLazyLattice passes it where
-    native_rows_grad_f64 sends a float64 product here); without it there is none and RectangularLazyLattice keeps the
+    native_rows_grad_f64 sends a float64 product here, or native_rows_grad a float32 one); without it there is none and RectangularLazyLattice keeps the
     padded path for that.  It is py:113-123 split by sides -- the incoming gradient lives on the out rows only, the
     right-hand side on the source rows only -- into two one-sided calls on the derivative-tap lattice of the stacked
-    positions (Lattice.apply_backward_rows), added into one zero [n, d] tensor; grad_source is then
+    positions (Lattice.apply_backward_rows; for float32 positions Lattice.apply_backward_rows_f32,
+    section 22), added into one zero [n, d] tensor; grad_source is then
     the derivative-tap filter of the incoming gradient, as LatticeFilterGeneral.backward returns it (py:123)."""
 
     @staticmethod
@@ -355,10 +356,10 @@ class LatticeRowsProduct(Function):
                 g = grad_output.contiguous()
                 lat = _cache.get(positions, ctx.deriv_coeffs)     # the derivative-tap lattice of the stacked positions
                 # a = g on the out rows, b = source on the source rows: the source rows' positions (and wg on them)
-                grad_in, grad_source = lat.apply_backward_rows(g, ob, source, sb, positions,
-                                                               want_filtered=ctx.needs_input_grad[0])
+                one_side = lat.apply_backward_rows_f32 if positions.dtype == torch.float32 else lat.apply_backward_rows
+                grad_in, grad_source = one_side(g, ob, source, sb, positions, want_filtered=ctx.needs_input_grad[0])
                 # a = source on the source rows, b = g on the out rows: the out rows' positions
-                grad_out, _ = lat.apply_backward_rows(source, sb, g, ob, positions, want_filtered=False)
+                grad_out, _ = one_side(source, sb, g, ob, positions, want_filtered=False)
                 grad_positions = torch.zeros_like(positions)
                 grad_positions[sb:sb + sc] += grad_in
                 grad_positions[ob:ob + oc] += grad_out
@@ -370,7 +371,7 @@ class LatticeRowsProduct(Function):
 
 
 def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1, f64=False,
-               grad_f64=False):
+               grad_f64=False, grad_f32=False):
     """Whether K(xin, xout) @ V goes through the native row-range product: a CUDA fp32 2-D right-hand side -- or, with
     f64=True (RectangularLazyLattice.native_rows_f64), a float64 one --, no test hook / foreign filter installed
     (LatticeFilterGeneral.method), no gradient wanted for the positions, the route switched on
@@ -380,7 +381,13 @@ def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, colum
     grad_f64=True (RectangularLazyLattice.native_rows_grad_f64) asks the other question: whether a product whose positions
     DO want a gradient goes through the native route with its native float64 position gradient.  That admits only a CUDA
     float64 2-D right-hand side with requires_grad set, no hook, the route switched on; the width gate does not apply
-    (it was measured for the fp32 forward)."""
+    (it was measured for the fp32 forward).
+
+    grad_f32=True (RectangularLazyLattice.native_rows_grad) asks the same of the native fp32 position gradient: only a CUDA
+    float32 2-D right-hand side with requires_grad set, no hook, the route switched on; no width gate either."""
+    if grad_f32:
+        return bool(enabled and device_type == "cuda" and dtype == torch.float32 and dim == 2 and hook is None
+                    and requires_grad)
     if grad_f64:
         return bool(enabled and device_type == "cuda" and dtype == torch.float64 and dim == 2 and hook is None
                     and requires_grad)
@@ -443,12 +450,18 @@ class RectangularLazyLattice(LazyTensor):
     points) must accept rows and Lattice.backward_rows_f64_ok must hold; native_min_columns does not apply (it was
     measured for the fp32 forward).  The two routes agree to rounding.  Off until the native route has been measured no
     slower than the padded one at every shape of tools/rows_backward_f64_time.py
-    (profiles/rows_backward_f64_measured.md)."""
+    (profiles/rows_backward_f64_measured.md).
+
+    native_rows_grad: the same for a float32 2-D V whose positions want a gradient (Lattice.apply_backward_rows_f32,
+    DESIGN.md section 22): both lattices must accept rows and Lattice.backward_rows_ok must hold; no width gate.  The two
+    routes agree to rounding.  On only if the native route is no slower than the padded one at every shape of
+    tools/rows_backward_time.py (profiles/rows_backward_measured.md says which it is, and which shapes lose)."""
 
     native_rows = True
     native_min_columns = 101
     native_rows_f64 = False
     native_rows_grad_f64 = False
+    native_rows_grad = False
 
     def __init__(self, xin, xout, dkernel=None):
         super().__init__(xin, xout, dkernel=dkernel)
@@ -471,10 +484,14 @@ class RectangularLazyLattice(LazyTensor):
                 nb_out = base.xout.shape[-2]
                 src_begin, out_begin = (nb_out, 0) if swapped else (0, nb_out)
                 return LatticeRowsProduct.apply(V, stacked, coeffs, lat, src_begin, out_begin, n_in)
-        elif (type(self).native_rows_grad_f64
-              and rows_route(V.device.type, V.dtype, V.dim(), LatticeFilterGeneral.method, wants_grad, type(self).native_rows,
-                             grad_f64=True)
-              and Lattice.backward_rows_f64_ok(V.shape[-1], self.xin.shape[-1])):
+        elif ((type(self).native_rows_grad_f64
+               and rows_route(V.device.type, V.dtype, V.dim(), LatticeFilterGeneral.method, wants_grad, type(self).native_rows,
+                              grad_f64=True)
+               and Lattice.backward_rows_f64_ok(V.shape[-1], self.xin.shape[-1]))
+              or (type(self).native_rows_grad
+                  and rows_route(V.device.type, V.dtype, V.dim(), LatticeFilterGeneral.method, wants_grad,
+                                 type(self).native_rows, grad_f32=True)
+                  and Lattice.backward_rows_ok(V.shape[-1], self.xin.shape[-1]))):
             base, swapped = self.__dict__.get("_rows_base", (self, False))
             stacked = base._stacked_points()                       # the concatenation WITH its gradient history
             coeffs = self.dkernel.get_coeffs()
