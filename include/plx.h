@@ -378,6 +378,44 @@ int plx_apply_affine_f64(plx_lattice *lat, const double *d_src, int vd, double *
                          double *d_dot, double *d_work, void *stream);
 
 /*
+ * The transposed and the symmetrised float64 products (callers detect them by symbol; the version string is unchanged).
+ * K = S B_d ... B_0 S^T / (1 + 2^-d) is not symmetric.  On a plain build the neighbour table is symmetric, so the
+ * transpose of one axis blur is that axis with mirrored taps (c'[i] = c[2 r - i]) and K^T runs the axes d .. 0 with them.
+ * K_s = (K + K^T) / 2 is symmetric to rounding; it is NOT proven positive (its smallest eigenvalue was -0.016 against a
+ * largest of 378 on one measured lattice), but plain CG converges on K_s + noise I at noise levels where it stalls on K.
+ *   plx_blur_t_f64        the adjoint of plx_blur_f64, with its arguments: the kernels of plx_blur_f64, host code only.
+ *   plx_apply_t_f64       splat -> blur_t -> slice: K^T d_src, on the workspace of plx_apply_f64.
+ *   plx_blur_sym_f64      0.5 (blur(values) + blur_t(values)) in d + 1 launches, each advancing both chains
+ *                         (f64_blur_dual_kernel): launch k takes the forward chain through axis k, the reverse chain
+ *                         through axis d - k; the first reads the one input plane for both, the last stores the one mean.
+ *                         d_work: plx_blur_sym_work_doubles(lat, vd) doubles (min(d + 1, 3) planes of m * stride; -1 for
+ *                         vd < 1 or an unbuilt lattice), 16-byte aligned for vd > 1, not overlapping d_values.  *d_result
+ *                         is set on the host, without synchronisation, to d_values or to a plane of d_work: where the
+ *                         result lies.  d_values is clobbered.
+ *   plx_apply_sym_f64     splat -> blur_sym -> slice: K_s d_src.  Runs on the workspace of plx_apply_f64 and two further
+ *                         planes that the first such call of a width allocates.
+ *   plx_apply_affine_sym_f64  plx_apply_affine_f64 with K_s for K: d_out = a K_s d_src + b d_src, the same arguments, the
+ *                         same affine slice kernels for the tail and d_dot (plx_affine_dot_work_doubles).
+ *   plx_last_sym_f64_kernels  "splat=...;blur=...;slice=..." of the last transposed or symmetrised call.  These calls leave
+ *                         what plx_last_f64_kernels reports untouched.
+ * Scope, refusals, alignment, the 2^31 limits and the capture rule are those of plx_apply_f64; a build that replayed
+ * "reference_growth" returns PLX_ERR_STATE because its neighbour table is not symmetric, so the reverse-axes identity does
+ * not hold there.  After the first call of a width, no call allocates or synchronises.
+ * Bit contracts: each chain's sums are formed as plx_blur_f64 forms them (same slots, same order, same fmas), the mean is
+ * one rounded sum and an exact halving, so plx_blur_sym_f64 gives the bits of 0.5 * (plx_blur_f64 + plx_blur_t_f64) formed
+ * in double by the caller; the staged calls give the bits of plx_apply_t_f64 and plx_apply_sym_f64; with (a, b) = (1, 0)
+ * plx_apply_affine_sym_f64 equals plx_apply_sym_f64 as values.  No atomics: two calls with the same arguments are bit-equal.
+ */
+int plx_blur_t_f64(plx_lattice *lat, double *d_values, double *d_scratch, int vd, int *result_in_scratch, void *stream);
+int plx_apply_t_f64(plx_lattice *lat, const double *d_src, int vd, double *d_out, void *stream);
+int64_t plx_blur_sym_work_doubles(const plx_lattice *lat, int vd);
+int plx_blur_sym_f64(plx_lattice *lat, double *d_values, double *d_work, int vd, double **d_result, void *stream);
+int plx_apply_sym_f64(plx_lattice *lat, const double *d_src, int vd, double *d_out, void *stream);
+int plx_apply_affine_sym_f64(plx_lattice *lat, const double *d_src, int vd, double *d_out, const double *d_scale_shift,
+                             double *d_dot, double *d_work, void *stream);
+int plx_last_sym_f64_kernels(const plx_lattice *lat, char *buf, int cap);
+
+/*
  * The float64 position gradient (callers detect it by symbol; the version string is unchanged): plx_apply_backward with
  * every array in double, for every column count.  `lat` is built with the DERIVATIVE taps on the positions rounded to
  * float, as for every fp64 call; d_x [n][d] is the caller's FLOAT64 position matrix (not the rounded copy), d_g (the

@@ -77,6 +77,13 @@ _SIGNATURES = {
     "plx_cg_step_direction_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i64, _i32, _vp, _vp, _vp]),
     "plx_affine_dot_work_doubles": (_i64, [_vp, _i32]),
     "plx_apply_affine_f64": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plx_blur_t_f64": (_i32, [_vp, _vp, _vp, _i32, ctypes.POINTER(_i32), _vp]),
+    "plx_apply_t_f64": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "plx_blur_sym_work_doubles": (_i64, [_vp, _i32]),
+    "plx_blur_sym_f64": (_i32, [_vp, _vp, _vp, _i32, ctypes.POINTER(_vp), _vp]),
+    "plx_apply_sym_f64": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "plx_apply_affine_sym_f64": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plx_last_sym_f64_kernels": (_i32, [_vp, ctypes.c_char_p, _i32]),
     "plx_backward_splat_f64": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "plx_backward_contract_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "plx_apply_backward_f64": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
@@ -159,7 +166,9 @@ OPTIONAL_SYMBOLS = frozenset(("plx_pcg_work_doubles", "plx_pcg_gram_f64", "plx_p
                               "plx_lanczos_step_f64", "plx_exact_work_bytes_f64", "plx_exact_splits_f64", "plx_exact_mvm_f64",
                               "plx_exact_grad_f64", "plx_backward_splat_rows_f64", "plx_backward_contract_rows_f64",
                               "plx_apply_backward_rows_f64", "plx_backward_splat_rows", "plx_backward_contract_rows",
-                              "plx_apply_backward_rows"))
+                              "plx_apply_backward_rows", "plx_blur_t_f64", "plx_apply_t_f64", "plx_blur_sym_work_doubles",
+                              "plx_blur_sym_f64", "plx_apply_sym_f64", "plx_apply_affine_sym_f64",
+                              "plx_last_sym_f64_kernels"))
 
 
 def declared_symbols():

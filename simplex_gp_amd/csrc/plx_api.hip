@@ -83,7 +83,7 @@ static std::vector<DevBuf *> all_bufs(plx_lattice *L)
             &L->head_partial, &L->tail_partial, &L->val_a, &L->val_b, &L->ssrc, &L->rec, &L->perm, &L->iota, &L->cmask, &L->cbase, &L->cids, &L->merge_slot, &L->merge_flags,
             &L->sortkey_in, &L->sortkey_out,
             &L->bc_pt, &L->bc_w, &L->srow, &L->brow_ptr, &L->brow_vid, &L->s2_idx, &L->s2_ptr, &L->s2_vid, &L->s2_wave, &L->s2_wave_v, &L->partial, &L->pair_nbr, &L->inv_perm, &L->vslot, &L->vkeys_alt, &L->vslot_alt, &L->vorder,
-            &L->rows_cnt, &L->rows_vid, &L->val64_a, &L->val64_b};
+            &L->rows_cnt, &L->rows_vid, &L->val64_a, &L->val64_b, &L->val64_s};
     for (auto &r : L->rows)
         for (DevBuf *b : {&r.ptr, &r.row, &r.w, &r.pos, &r.prow}) v.push_back(b);
     return v;
@@ -670,6 +670,141 @@ int plx_last_f64_kernels(const plx_lattice *L, char *buf, int cap)
 {
     if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
     snprintf(buf, (size_t)cap, "splat=%s;blur_axis=%s;slice=%s", L->kn_f64_splat, L->kn_f64_blur, L->kn_f64_slice);
+    return PLX_OK;
+}
+
+// ---- the transposed and symmetrised float64 products (kernels: plx_sym_f64.hip around those of plx_f64.hip) -------------
+
+// The stage implementations name their kernels in the kn_f64_* fields: a transposed or symmetrised call moves what it
+// launched to the kn_sym_* fields and leaves plx_last_f64_kernels with what the last plain call reported.
+struct SymKernelNames {
+    plx_lattice *L;
+    const char *splat, *blur, *slice;
+    explicit SymKernelNames(plx_lattice *lat) : L(lat), splat(lat->kn_f64_splat), blur(lat->kn_f64_blur), slice(lat->kn_f64_slice)
+    {
+        L->kn_f64_splat = L->kn_f64_blur = L->kn_f64_slice = L->kn_sym_splat = L->kn_sym_blur = L->kn_sym_slice = "";
+    }
+    ~SymKernelNames()
+    {
+        if (*L->kn_f64_splat) L->kn_sym_splat = L->kn_f64_splat;
+        if (*L->kn_f64_blur) L->kn_sym_blur = L->kn_f64_blur;
+        if (*L->kn_f64_slice) L->kn_sym_slice = L->kn_f64_slice;
+        L->kn_f64_splat = splat;
+        L->kn_f64_blur = blur;
+        L->kn_f64_slice = slice;
+    }
+};
+
+int plx_blur_t_f64(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_values, d_scratch, vd, "plx_blur_t_f64"));
+    if (!result_in_scratch) { set_error("plx_blur_t_f64: result_in_scratch is NULL"); return PLX_ERR_INVALID; }
+    if (d_values == d_scratch) { set_error("plx_blur_t_f64: d_values and d_scratch must be different buffers"); return PLX_ERR_INVALID; }
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_t_f64"));
+    PLX_TRY(check_values_aligned(d_scratch, vd, "plx_blur_t_f64"));
+    DeviceGuard g(L->device);
+    SymKernelNames kn(L);
+    return blur_t_f64_impl(L, d_values, d_scratch, vd, result_in_scratch, (hipStream_t)stream);
+}
+
+int plx_apply_t_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_src, d_out, vd, "plx_apply_t_f64"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    PLX_TRY(ensure(L->val64_a, (size_t)L->m * values_stride_f64(vd) * 8));      // the workspace of plx_apply_f64
+    PLX_TRY(ensure(L->val64_b, (size_t)L->m * values_stride_f64(vd) * 8));
+    SymKernelNames kn(L);
+    PLX_TRY(splat_f64_impl(L, d_src, vd, L->val64_a.as<double>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_t_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), vd, &in_b, s));
+    return slice_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, d_out, s);
+}
+
+int64_t plx_blur_sym_work_doubles(const plx_lattice *L, int vd)
+{
+    if (!L || !L->built || vd < 1) return -1;
+    return (int64_t)blur_sym_f64_planes(L) * L->m * values_stride_f64(vd);
+}
+
+int plx_blur_sym_f64(plx_lattice *L, double *d_values, double *d_work, int vd, double **d_result, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_values, d_work, vd, "plx_blur_sym_f64"));
+    if (!d_result) { set_error("plx_blur_sym_f64: d_result is NULL"); return PLX_ERR_INVALID; }
+    const double *work_end = d_work + plx_blur_sym_work_doubles(L, vd), *values_end = d_values + (size_t)L->m * values_stride_f64(vd);
+    if (d_values < work_end && d_work < values_end) {
+        set_error("plx_blur_sym_f64: d_values and d_work (plx_blur_sym_work_doubles) must not overlap");
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_sym_f64"));
+    PLX_TRY(check_values_aligned(d_work, vd, "plx_blur_sym_f64"));
+    DeviceGuard g(L->device);
+    SymKernelNames kn(L);
+    L->kn_f64_blur = "f64_blur_dual_kernel";
+    const size_t plane = (size_t)L->m * values_stride_f64(vd);
+    double *planes[3] = {d_work, d_work + plane, d_work + 2 * plane};      // (the last ones unused where d + 1 < 3)
+    return blur_sym_f64_impl(L, d_values, planes, vd, d_result, (hipStream_t)stream);
+}
+
+// splat + symmetrised blur on the lattice's fp64 workspace: val64_a holds the splat, val64_b and the two planes of val64_s
+// are the work space; *d_blurred: the plane the slice reads
+static int splat_blur_sym_f64(plx_lattice *L, const double *d_src, int vd, double **d_blurred, hipStream_t s)
+{
+    const size_t plane = (size_t)L->m * values_stride_f64(vd);
+    PLX_TRY(ensure(L->val64_a, plane * 8));      // the workspace of plx_apply_f64
+    PLX_TRY(ensure(L->val64_b, plane * 8));
+    PLX_TRY(ensure(L->val64_s, 2 * plane * 8));
+    PLX_TRY(splat_f64_impl(L, d_src, vd, L->val64_a.as<double>(), s));
+    // the three work planes need not be contiguous here: the symmetrised blur takes them one by one
+    L->kn_f64_blur = "f64_blur_dual_kernel";
+    double *planes[3] = {L->val64_b.as<double>(), L->val64_s.as<double>(), L->val64_s.as<double>() + plane};
+    return blur_sym_f64_impl(L, L->val64_a.as<double>(), planes, vd, d_blurred, s);
+}
+
+int plx_apply_sym_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_src, d_out, vd, "plx_apply_sym_f64"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    SymKernelNames kn(L);
+    double *blurred = nullptr;
+    PLX_TRY(splat_blur_sym_f64(L, d_src, vd, &blurred, s));
+    return slice_f64_impl(L, blurred, vd, d_out, s);
+}
+
+int plx_apply_affine_sym_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, const double *d_scale_shift, double *d_dot,
+                             double *d_work, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_f64(L, d_src, d_out, vd, "plx_apply_affine_sym_f64"));
+    if (!d_scale_shift) { set_error("plx_apply_affine_sym_f64: NULL scale/shift"); return PLX_ERR_INVALID; }
+    if (d_dot && !d_work) { set_error("plx_apply_affine_sym_f64: d_dot needs d_work (plx_affine_dot_work_doubles)"); return PLX_ERR_INVALID; }
+    PLX_TRY(check_doubles_aligned(d_scale_shift, d_dot, "plx_apply_affine_sym_f64"));
+    PLX_TRY(check_doubles_aligned(d_work, nullptr, "plx_apply_affine_sym_f64"));
+    if (d_src == d_out) { set_error("plx_apply_affine_sym_f64: d_out must not alias d_src"); return PLX_ERR_INVALID; }
+    const int dot_rows = d_dot ? affine_f64_dot_rows(L, vd) : 0;
+    if (d_dot && dot_rows < 1) {
+        set_error("plx_apply_affine_sym_f64: the fused dot serves vd <= 128, got %d (pass d_dot = NULL and use plx_coldot_f64)", vd);
+        return PLX_ERR_INVALID;
+    }
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    SymKernelNames kn(L);
+    double *blurred = nullptr;
+    PLX_TRY(splat_blur_sym_f64(L, d_src, vd, &blurred, s));
+    PLX_TRY(slice_affine_f64_impl(L, blurred, vd, d_src, d_scale_shift, d_out, d_dot ? d_work : nullptr, s));
+    if (!d_dot) return PLX_OK;
+    return coldot_final_f64(d_work, dot_rows, values_stride_f64(vd), vd, d_dot, s);
+}
+
+int plx_last_sym_f64_kernels(const plx_lattice *L, char *buf, int cap)
+{
+    if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
+    snprintf(buf, (size_t)cap, "splat=%s;blur=%s;slice=%s", L->kn_sym_splat, L->kn_sym_blur, L->kn_sym_slice);
     return PLX_OK;
 }
 

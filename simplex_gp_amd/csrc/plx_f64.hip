@@ -110,8 +110,6 @@ __device__ __forceinline__ void f64_blur_item(const V *__restrict__ old, V *__re
     out[item] = acc;
 }
 
-struct TapArgs64 { double c[2 * PLX_MAX_ORDER + 1]; };
-
 template <int ORDER>
 __global__ __launch_bounds__(kBlock) void f64_blur_v1_kernel(const double *__restrict__ old, double *__restrict__ out,
                                                              const int *__restrict__ nbr, int m, int64_t mstride,
@@ -250,22 +248,28 @@ static void launch_blur_f64(plx_lattice *L, const double *old, double *out, cons
             ntiles);
 }
 
+void blur_axis_f64(plx_lattice *L, const double *old, double *out, int axis, int vd, const TapArgs64 &taps, hipStream_t stream)
+{
+    const int order = L->order;
+    const int *nbr = L->nbr.as<int>() + (size_t)axis * 2 * order * L->mstride;
+    L->kn_f64_blur = vd == 1 ? "f64_blur_v1_kernel" : "f64_blur_chunk_kernel";
+    switch (order) {
+    case 0: launch_blur_f64<0>(L, old, out, nbr, vd, taps, stream); break;
+    case 1: launch_blur_f64<1>(L, old, out, nbr, vd, taps, stream); break;
+    case 2: launch_blur_f64<2>(L, old, out, nbr, vd, taps, stream); break;
+    case 3: launch_blur_f64<3>(L, old, out, nbr, vd, taps, stream); break;
+    default: launch_blur_f64<-1>(L, old, out, nbr, vd, taps, stream); break;
+    }
+}
+
 int blur_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream)
 {
-    const int d1 = L->d + 1, order = L->order;
+    const int d1 = L->d + 1;
     TapArgs64 taps;
     for (int i = 0; i < 2 * PLX_MAX_ORDER + 1; ++i) taps.c[i] = (double)L->taps.c[i];
-    L->kn_f64_blur = vd == 1 ? "f64_blur_v1_kernel" : "f64_blur_chunk_kernel";
     double *cur = d_values, *nxt = d_scratch;
     for (int a = 0; a < d1; ++a) {
-        const int *nbr = L->nbr.as<int>() + (size_t)a * 2 * order * L->mstride;
-        switch (order) {
-        case 0: launch_blur_f64<0>(L, cur, nxt, nbr, vd, taps, stream); break;
-        case 1: launch_blur_f64<1>(L, cur, nxt, nbr, vd, taps, stream); break;
-        case 2: launch_blur_f64<2>(L, cur, nxt, nbr, vd, taps, stream); break;
-        case 3: launch_blur_f64<3>(L, cur, nxt, nbr, vd, taps, stream); break;
-        default: launch_blur_f64<-1>(L, cur, nxt, nbr, vd, taps, stream); break;
-        }
+        blur_axis_f64(L, cur, nxt, a, vd, taps, stream);
         std::swap(cur, nxt);
     }
     *result_in_scratch = cur == d_scratch ? 1 : 0;

@@ -44,6 +44,7 @@ struct DevBuf {
 
 struct ScaleArgs { float v[PLX_MAX_DIM]; };              // h:372-390 scale factors
 struct TapArgs { float c[2 * PLX_MAX_ORDER + 1]; };      // blur weights, h:546
+struct TapArgs64 { double c[2 * PLX_MAX_ORDER + 1]; };   // ... converted exactly to double (the float64 blurs)
 
 // Kernel-variant switches (plx_tune).  The process-wide defaults live in g_tune_defaults; every lattice takes a snapshot
 // when a build starts (plx_build / plx_build_local / plx_filter) and every entry point serves its lattice under that
@@ -303,6 +304,11 @@ struct plx_lattice {
     // per-launch timing of plx_apply (timing on): events between consecutive launches
     hipEvent_t tev[PLX_MAX_DIM + 8] = {};
     int tev_n = 0;
+
+    // the transposed and symmetrised float64 products (plx_sym_f64.hip): the two further value planes of the symmetrised
+    // blur, allocated by the first plx_apply_sym_f64 of a width, and the kernels of the last such call
+    plx::DevBuf val64_s;                      // double [2][m][plx_values_stride_f64(vd)]
+    const char *kn_sym_splat = "", *kn_sym_blur = "", *kn_sym_slice = "";   // plx_last_sym_f64_kernels
 };
 
 namespace plx {
@@ -387,6 +393,14 @@ int slice_rows_f64_impl(plx_lattice *L, const double *d_values, int vd, int64_t 
 int splat_f64_impl(plx_lattice *L, const double *d_src, int vd, double *d_values, hipStream_t stream);
 int blur_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
 int slice_f64_impl(plx_lattice *L, const double *d_values, int vd, double *d_out, hipStream_t stream);
+// ... and one axis of the blur with the taps given: out = B_axis old (old != out), the launch blur_f64_impl makes per axis
+void blur_axis_f64(plx_lattice *L, const double *old, double *out, int axis, int vd, const TapArgs64 &taps, hipStream_t stream);
+// plx_sym_f64.hip: the transposed blur (axes d .. 0, mirrored taps, the kernels of plx_f64.hip) and the symmetrised one,
+// 0.5 (blur + blur_t), both chains advanced by each of d + 1 launches.  blur_sym_f64_planes: planes of m * stride doubles
+// the symmetrised blur needs beside d_values (1, 2 or 3 of d_work[], in that order); *d_result: d_values or one of them.
+int blur_t_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
+int blur_sym_f64_planes(const plx_lattice *L);
+int blur_sym_f64_impl(plx_lattice *L, double *d_values, double *const d_work[3], int vd, double **d_result, hipStream_t stream);
 // plx_cg_f64.hip: the fp64 slice with the affine tail out = a y + b src fused (and, unless d_partial is NULL, one partial
 // row of <src, out> per workgroup: affine_f64_dot_rows rows of values_stride_f64(vd) doubles; 0 rows: the shape serves no
 // dot), and the final stage of plx_coldot_f64: out[c] = sum over nrows of partial[k * stride + c], c < vd, fixed order

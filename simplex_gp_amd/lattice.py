@@ -409,6 +409,93 @@ class Lattice:
         "blur_axis": [...], "slice": [...]}; stage_kernels() goes on naming the fp32 stages."""
         return self._last_kernels("plx_last_f64_kernels", 256)
 
+    # -- the transposed and symmetrised float64 products (plx_*_t_f64 / plx_*_sym_f64) ------
+    # K is not symmetric (the axis blurs do not commute).  K^T runs the axes in reverse with mirrored taps; K_s = (K + K^T) / 2
+    # advances both blur chains in each of its d + 1 launches.  float64 only: the fp32 blur's kernel families carry
+    # order-dependent pair stencils, so its transpose is not served.
+    @staticmethod
+    def _f64_only(t, name, what):
+        if isinstance(t, torch.Tensor) and t.dtype != torch.float64:
+            raise TypeError(f"{what} is served in float64 only (the transposed and symmetrised lattice products have no "
+                            f"fp32 form), got {name} of {t.dtype}")
+
+    def blur_t(self, values, scratch=None, vd=None):
+        """The adjoint of the float64 blur(): axes d .. 0, mirrored taps (plx_blur_t_f64).  Returns the tensor that holds
+        the result (either `values` or `scratch`), as blur() does."""
+        self._f64_only(values, "values", "blur_t")
+        _check_f32_cuda(values, "values", f64_ok=True)
+        vd = values.shape[1] if vd is None else vd
+        assert values.shape[1] == self.values_stride(vd, values.dtype) and values.is_contiguous()
+        if values.shape[0] < self.m:
+            raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
+        if scratch is None:
+            scratch = torch.empty_like(values)
+        elif scratch.numel() < values.numel() or not scratch.is_contiguous() or scratch.dtype != values.dtype:
+            raise ValueError("scratch must be a contiguous buffer of the values' dtype, at least as large as values")
+        flag = ctypes.c_int(0)
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_blur_t_f64(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), vd,
+                                         ctypes.byref(flag), _stream_ptr(self.device))
+        nv.check(rc, "plx_blur_t_f64")
+        return scratch if flag.value else values
+
+    def blur_sym(self, values, work=None, vd=None):
+        """0.5 * (blur(values) + blur_t(values)) in d + 1 launches that advance both chains (plx_blur_sym_f64).  `values`
+        [m, values_stride(vd)] float64 is clobbered; `work`: a contiguous float64 buffer of at least
+        plx_blur_sym_work_doubles elements (allocated when None).  Returns an [m, stride] tensor that views `values` or
+        `work`, wherever the result lies."""
+        self._f64_only(values, "values", "blur_sym")
+        _check_f32_cuda(values, "values", f64_ok=True)
+        vd = values.shape[1] if vd is None else vd
+        stride = self.values_stride(vd, values.dtype)
+        assert values.shape[1] == stride and values.is_contiguous()
+        if values.shape[0] < self.m:
+            raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
+        need = int(nv.lib().plx_blur_sym_work_doubles(self._h, vd))
+        if need < 0:
+            raise ValueError(f"blur_sym needs a built lattice and vd >= 1, got vd = {vd}")
+        if work is None:
+            work = torch.empty(need, dtype=torch.float64, device=self.device)
+        elif work.numel() < need or not work.is_contiguous() or work.dtype != torch.float64:
+            raise ValueError(f"work must be a contiguous float64 buffer of at least {need} elements")
+        res = ctypes.c_void_p(0)
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_blur_sym_f64(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(work.data_ptr()), vd,
+                                           ctypes.byref(res), _stream_ptr(self.device))
+        nv.check(rc, "plx_blur_sym_f64")
+        if res.value == values.data_ptr():
+            return values[:self.m]
+        off = (res.value - work.data_ptr()) // 8
+        return work.view(-1)[off:off + self.m * stride].view(self.m, stride)
+
+    def _apply_f64_variant(self, src, out, fn, what):
+        self._f64_only(src, "src", what)
+        src = self._src(src, self.n_owned, f64_ok=True)
+        vd = src.shape[1]
+        if out is None:
+            out = torch.empty((self.n_owned, vd), dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64:
+            raise TypeError(f"out must be torch.float64 like src, got {out.dtype}")
+        with torch.cuda.device(self.device):
+            rc = getattr(nv.lib(), fn)(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                                       _stream_ptr(self.device))
+        nv.check(rc, fn)
+        return out
+
+    def apply_t(self, src, out=None):
+        """out = K^T src: slice(blur_t(splat(src))) on the float64 workspace (plx_apply_t_f64).  float64 only."""
+        return self._apply_f64_variant(src, out, "plx_apply_t_f64", "apply_t")
+
+    def apply_sym(self, src, out=None):
+        """out = K_s src with K_s = (K + K^T) / 2: slice(blur_sym(splat(src))) (plx_apply_sym_f64).  float64 only.  K_s is
+        symmetric to rounding; it is not proven positive."""
+        return self._apply_f64_variant(src, out, "plx_apply_sym_f64", "apply_sym")
+
+    def sym_f64_kernels(self):
+        """Kernels launched by the last transposed or symmetrised float64 call: {"splat": [...], "blur": [...],
+        "slice": [...]}; f64_kernels() goes on naming the plain float64 stages."""
+        return self._last_kernels("plx_last_sym_f64_kernels", 256)
+
     # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
     def _rows(self, begin, count):
         begin, count = int(begin), int(count)
@@ -494,18 +581,21 @@ class Lattice:
             return False
         return not self.reference_growth_info()["replayed"]
 
-    def apply_affine(self, src, scale_shift, out=None, want_dot=False):
+    def apply_affine(self, src, scale_shift, out=None, want_dot=False, symmetric=False):
         """out = a * K src + b * src with (a, b) = scale_shift (a 2-element tensor on the device, of the dtype of `src`, read
         there: no host synchronisation on hyper-parameters).  float64: plx_apply_affine_f64, rows always in the caller's
         order, want_dot=True for up to 128 columns, no want_dot="partial"; a mixed pair is a TypeError.  want_dot: also return the column-wise <src, out>
         (the p^T A p of a CG iteration), formed inside the slice kernel; needs 2..256 columns.  want_dot="partial":
         return (out, work, tiles) with the per-tile partial sums of those dots left un-reduced in `work` (the fused CG
-        step adds them up itself); `work` is the lattice's own buffer, valid until the next such call."""
+        step adds them up itself); `work` is the lattice's own buffer, valid until the next such call.
+        symmetric=True (float64 only): K_s = (K + K^T) / 2 for K (plx_apply_affine_sym_f64), everything else unchanged."""
+        if symmetric:
+            self._f64_only(src, "src", "apply_affine(symmetric=True)")
         if isinstance(src, torch.Tensor) and isinstance(scale_shift, torch.Tensor) and src.dtype != scale_shift.dtype:
             raise TypeError(f"src and scale_shift must both be float32 or both float64, got {src.dtype} and "
                             f"{scale_shift.dtype}")
         if isinstance(src, torch.Tensor) and src.dtype == torch.float64:
-            return self._apply_affine_f64(src, scale_shift, out, want_dot)
+            return self._apply_affine_f64(src, scale_shift, out, want_dot, symmetric)
         src = self._src(src, self.n_owned)
         _check_f32_cuda(scale_shift, "scale_shift", ndim=1)
         assert scale_shift.numel() == 2 and scale_shift.is_contiguous()
@@ -545,8 +635,8 @@ class Lattice:
         """True when the float64 apply_affine(want_dot=True) serves vd columns on this build (plx_affine_dot_work_doubles)."""
         return int(nv.lib().plx_affine_dot_work_doubles(self._h, int(vd))) >= 0
 
-    def _apply_affine_f64(self, src, scale_shift, out, want_dot):
-        """The float64 form of apply_affine (plx_apply_affine_f64): rows in the caller's order, scale_shift a float64
+    def _apply_affine_f64(self, src, scale_shift, out, want_dot, symmetric=False):
+        """The float64 form of apply_affine (plx_apply_affine_f64; symmetric: plx_apply_affine_sym_f64): rows in the caller's order, scale_shift a float64
         2-vector on the device; want_dot=True for up to 128 columns; there is no fused CG step in double, hence no
         want_dot="partial"."""
         if want_dot == "partial":
@@ -569,12 +659,13 @@ class Lattice:
                 self._dot_work64 = torch.empty(need, dtype=torch.float64, device=self.device)
             work = self._dot_work64
             dot = torch.empty(vd, dtype=torch.float64, device=self.device)
+        name = "plx_apply_affine_sym_f64" if symmetric else "plx_apply_affine_f64"
         with torch.cuda.device(self.device):
-            rc = L.plx_apply_affine_f64(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
-                                        ctypes.c_void_p(scale_shift.data_ptr()),
-                                        ctypes.c_void_p(dot.data_ptr()) if want_dot else None,
-                                        ctypes.c_void_p(work.data_ptr()) if want_dot else None, _stream_ptr(self.device))
-        nv.check(rc, "plx_apply_affine_f64")
+            rc = getattr(L, name)(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                                  ctypes.c_void_p(scale_shift.data_ptr()),
+                                  ctypes.c_void_p(dot.data_ptr()) if want_dot else None,
+                                  ctypes.c_void_p(work.data_ptr()) if want_dot else None, _stream_ptr(self.device))
+        nv.check(rc, name)
         return (out, dot) if want_dot else out
 
     @staticmethod

@@ -233,6 +233,13 @@ class LatticeFilterGeneral(Function):
     # switch changes time and memory only.  Off until the native route has been measured no slower than the torch route
     # at the three shapes of tools/backward_f64_time.py (profiles/backward_f64_measured.md).
     fused_backward_f64 = False
+    # float64: True returns the EXACT adjoint for the gradient with respect to `source`: K^T g on the forward-tap lattice
+    # (Lattice.apply_t), in every branch of backward() that returns one -- K is not symmetric, so neither K g (py:110-111)
+    # nor the derivative-tap filter of g (py:123) is the adjoint of the forward product, and torch.autograd.gradcheck with
+    # respect to `source` fails without the switch.  Applies where `method` is None and the tensors are CUDA float64 2-D.
+    # The POSITION gradient is unchanged: it keeps the reference's symmetric treatment (py:113-122).  Off by default: the
+    # reference's gradients are what every existing caller and test sees.
+    exact_adjoint = False
 
     @staticmethod
     def _filter():
@@ -258,7 +265,10 @@ class LatticeFilterGeneral(Function):
             g = grad_output
             L = src.shape[-1]
             d = ref.shape[-1]
-            if ctx.needs_input_grad[0] and not ctx.needs_input_grad[1]:
+            exact = (LatticeFilterGeneral.exact_adjoint and LatticeFilterGeneral.method is None and ctx.needs_input_grad[0]
+                     and g.is_cuda and g.dim() == 2 and g.dtype == src.dtype == ref.dtype == torch.float64)
+            want_src = ctx.needs_input_grad[0] and not exact      # (exact: grad_source is formed once, at the end)
+            if want_src and not ctx.needs_input_grad[1]:
                 # K is treated as symmetric (py:110-111)
                 grad_source = filt(g.contiguous(), ref.contiguous(), ctx.coeffs)
             # float32: the fused and the three-call position gradients are fp32 kernels.  In double the gradient is one
@@ -278,10 +288,10 @@ class LatticeFilterGeneral(Function):
                 # the whole of py:113-123 in one native call: the stacked matrix is never stored (plx_apply_backward)
                 rc_ = ref if ref.is_contiguous() else carry_hint(ref.contiguous(), ref)
                 lat = _cache.get(rc_, ctx.deriv_coeffs)
-                grad_reference, grad_source = lat.apply_backward(g, src, rc_, want_grad_src=ctx.needs_input_grad[0])
+                grad_reference, grad_source = lat.apply_backward(g, src, rc_, want_grad_src=want_src)
             elif ctx.needs_input_grad[1] and lat64 is not None:
                 # the same in double: stack inside the splat, contraction inside the slice (plx_apply_backward_f64)
-                grad_reference, grad_source = lat64.apply_backward(g, src, rc_, want_grad_src=ctx.needs_input_grad[0])
+                grad_reference, grad_source = lat64.apply_backward(g, src, rc_, want_grad_src=want_src)
             elif ctx.needs_input_grad[1] and native:
                 # same computation, the stack and the contraction each as one native pass (plx_backward_*)
                 import ctypes
@@ -300,7 +310,7 @@ class LatticeFilterGeneral(Function):
                 with torch.cuda.device(g.device):
                     nv.check(nv.lib().plx_backward_contract(ptr(gc), ptr(sc), ptr(rc_), ptr(filtered), n, L, d,
                                                             ptr(grad_reference), stream), "plx_backward_contract")
-                if ctx.needs_input_grad[0]:
+                if want_src:
                     grad_source = filtered[:, :L].contiguous()   # filtered with the derivative taps (py:123)
             elif ctx.needs_input_grad[1]:
                 # one filter with the derivative taps over [g, g (x) x, src, src (x) x]   (py:113-119)
@@ -315,8 +325,12 @@ class LatticeFilterGeneral(Function):
                 # py:122
                 grad_reference = -2 * (sx * wg[..., None] - src[..., None] * wgx
                                        + gx * ws[..., None] - g[..., None] * wsx).sum(-2)
-                if ctx.needs_input_grad[0]:
+                if want_src:
                     grad_source = wg       # filtered with the derivative taps, as the reference does (py:123)
+            if exact:
+                # the adjoint of the forward product: K^T g with the forward taps (plx_apply_t_f64)
+                rc_ = ref if ref.is_contiguous() else carry_hint(ref.contiguous(), ref)
+                grad_source = _cache.get(rc_, ctx.coeffs).apply_t(g.contiguous())
         return grad_source, grad_reference, None
 
 
@@ -405,15 +419,24 @@ class SquareLazyLattice(LazyTensor):
     """K(x, x), known through its action only (py:127-140): symmetric by declaration (its transpose is itself,
     py:137-138) and with a unit diagonal by declaration (py:139-140), whatever the lattice actually computes."""
 
-    def __init__(self, x, dkernel=None):
-        super().__init__(x, dkernel=dkernel)
-        self.x, self.dkernel = x, dkernel
+    def __init__(self, x, dkernel=None, symmetrized=False):
+        super().__init__(x, dkernel=dkernel, symmetrized=symmetrized)
+        self.x, self.dkernel, self.symmetrized = x, dkernel, bool(symmetrized)
 
     def _size(self):
         n = self.x.shape[-2]
         return torch.Size((n, n))
 
     def _matmul(self, V):
+        if self.symmetrized and V.dtype == torch.float64:
+            # K_s = (K + K^T) / 2 on the forward-tap lattice (Lattice.apply_sym): symmetric to rounding, so the
+            # declaration below is then true of what is computed.  No autograd through this product.
+            if not (V.is_cuda and V.dim() == 2 and self.x.dtype == torch.float64):
+                raise TypeError("SquareLazyLattice(symmetrized=True) serves CUDA float64 2-D right-hand sides on float64 "
+                                "positions only")
+            x = self.x.detach()
+            x = x if x.is_contiguous() else carry_hint(x.contiguous(), x)
+            return _cache.get(x, self.dkernel.get_coeffs()).apply_sym(V.detach())
         return _lattice_matvec(V, self.x, self.dkernel)
 
     def _transpose_nonbatch(self):

@@ -1033,6 +1033,13 @@ class LatticeGP(nn.Module):
     """Constant mean + outputscale * LatticeKernel + Gaussian noise >= min_noise:
     the model of tests/train_snelson.py:11-23 / experiments/train_simplexgp.py:13-26."""
 
+    # float64: True runs the double model's CG and PCG solves (khat_solve) and whatever iterates on khat_in_lattice_rows
+    # (the Lanczos run of the variance cache) on s K_s + sigma^2 I with K_s = (K + K^T) / 2 (Lattice.apply_sym), the
+    # symmetric operator those iterations are defined for; K itself is not symmetric and plain CG stalls or diverges on it
+    # at small noise.  K_s is symmetric to rounding but NOT proven positive.  A pivoted-Cholesky preconditioner stays the
+    # factor built from K: it is a preconditioner, not the operator.  Off by default: the solves see what they always saw.
+    symmetric_f64 = False
+
     def __init__(self, kernel, min_noise=1e-4):
         super().__init__()
         assert isinstance(kernel, LatticeAccelerated)
@@ -1077,7 +1084,8 @@ class LatticeGP(nn.Module):
             if x.dtype == torch.float64:
                 # the float64 product keeps the caller's row order: the affine closure in double, identity permutations
                 ss = torch.stack([self.outputscale.detach().reshape(()), self.noise.detach().reshape(())]).to(torch.float64).contiguous()
-                yield (lambda V: lat.apply_affine(V.contiguous(), ss)), (lambda v: v), (lambda v: v)
+                sym = bool(self.symmetric_f64)
+                yield (lambda V: lat.apply_affine(V.contiguous(), ss, symmetric=sym)), (lambda v: v), (lambda v: v)
                 return
             ss = torch.stack([self.outputscale.detach().reshape(()), self.noise.detach().reshape(())]).to(torch.float32).contiguous()
             lat.set_lattice_row_order(True)
@@ -1168,7 +1176,7 @@ class LatticeGP(nn.Module):
             lat = lk.lattice_cache().get(ref, self.kernel.dkernel_fn.get_coeffs())
             s, noise = self.outputscale, self.noise
             if rhs.dtype == torch.float64:
-                return self._khat_solve_f64(lat, rhs, s, noise, cg_args)
+                return self._khat_solve_f64(lat, rhs, s, noise, cg_args, symmetric=bool(self.symmetric_f64))
             lat.set_lattice_row_order(True)
             try:
                 native_pre = isinstance(pre, LatticePreconditioner) and pre.lat is lat and pre.build_id == lat.build_id
@@ -1207,26 +1215,28 @@ class LatticeGP(nn.Module):
             return lat.from_lattice_order(sol), info
 
     @staticmethod
-    def _khat_solve_f64(lat, rhs, s, noise, cg_args):
+    def _khat_solve_f64(lat, rhs, s, noise, cg_args, symmetric=False):
         """khat_solve for a float64 right-hand side: the float64 product takes and returns rows in the caller's order, so
         nothing is permuted and the lattice's row order is never touched; no column padding either (fp64 rows need 8-byte
         alignment only, and 16-byte accesses follow from an even column count).  Every MVM is plx_apply_affine_f64, with
-        <P, AP> out of its slice kernel where the width allows."""
+        <P, AP> out of its slice kernel where the width allows.  symmetric: K_s = (K + K^T) / 2 for K in every MVM
+        (plx_apply_affine_sym_f64 / plx_apply_sym_f64); a preconditioner's factor is left as it was built."""
         pre = cg_args.get("precond")
         native_pre = isinstance(pre, LatticePreconditioner64) and NATIVE_PCG_F64 and pre.lat is lat \
             and pre.build_id == lat.build_id and rhs.dim() == 2 and 1 <= rhs.shape[1] <= 16 and cg_args.get("reduce") is None
         if pre is not None and not native_pre:
             # the caller-order branch of the fp32 solve: its factor's rows are in the caller's order too
-            return batched_cg(lambda V: lat.apply(V).mul_(s).addcmul_(V, noise), rhs, **cg_args)
+            product = lat.apply_sym if symmetric else lat.apply
+            return batched_cg(lambda V: product(V).mul_(s).addcmul_(V, noise), rhs, **cg_args)
         ss = torch.stack([s.detach().reshape(()), noise.detach().reshape(())]).to(torch.float64).contiguous()
         rhs = rhs.contiguous()
         fused_dot = None
         if lat.affine_dot_f64_ok(rhs.shape[1]):
             def fused_dot(V):
-                return lat.apply_affine(V, ss, want_dot=True)
+                return lat.apply_affine(V, ss, want_dot=True, symmetric=symmetric)
         # (a native preconditioner's rows are in the caller's order like the product's)
-        return batched_cg(lambda V: lat.apply_affine(V.contiguous(), ss), rhs, matmul_dot=fused_dot, native_precond=native_pre,
-                          **cg_args)
+        return batched_cg(lambda V: lat.apply_affine(V.contiguous(), ss, symmetric=symmetric), rhs, matmul_dot=fused_dot,
+                          native_precond=native_pre, **cg_args)
 
     def preconditioner(self, x, rank, K=None, factor_dtype=torch.float16):
         """Rank-`rank` pivoted-Cholesky preconditioner of (s K + sigma^2 I) (no gradients).  On the HIP path it is
