@@ -495,7 +495,9 @@ int plx_apply_backward_f64(plx_lattice *lat, const double *d_g, const double *d_
  * The splat and the contraction report through plx_last_rows_f64_kernels (rows64_backward_splat_chunk_kernel /
  * rows64_backward_splat_wide_kernel in the splat field, rows64_backward_contract_chunk_kernel /
  * rows64_backward_contract_wide_kernel in the slice field: the chunk shape up to 64 chunks, i.e. stride <= 128, the wide
- * shape above); the blur reports through plx_last_f64_kernels.
+ * shape above); the blur reports through plx_last_f64_kernels.  These are the names the library reports; the kernels are the
+ * double instances of the templates the fp32 form below shares (csrc/plx_rows_backward_kernels.h), so a profiler shows the
+ * symbols rows_backward_splat_chunk_kernel<double> ... rows_backward_contract_wide_kernel<double, D1>.
  * Scope, refusals, workspace growth and the capture rule are those of plx_apply_rows_f64 and plx_apply_backward_f64 together.
  * PLX_ERR_STATE: a lattice that is not built, a sharded or merged build, a build that replayed "reference_growth", and under
  * stream capture a call that would have to build a range table, make the vertex row pointer or grow the workspace.
@@ -554,7 +556,7 @@ int plx_apply_backward_rows_f64(plx_lattice *lat, const double *d_a, int64_t a_b
  * The splat and the contraction report through plx_last_rows_kernels (rows_backward_splat_chunk_kernel /
  * rows_backward_splat_wide_kernel in the splat field, rows_backward_contract_chunk_kernel /
  * rows_backward_contract_wide_kernel in the slice field: the chunk shape up to 64 chunks, i.e. stride <= 256, the wide shape
- * above); the blur reports through plx_last_kernels.
+ * above; a profiler shows the symbols with <float> or <float, D1> appended); the blur reports through plx_last_kernels.
  * PLX_ERR_STATE: a lattice that is not built, a sharded or merged build, a build that replayed "reference_growth", and under
  * stream capture a call that would have to build a range table or grow the workspace.  PLX_ERR_INVALID: a NULL pointer other
  * than d_filtered, nrhs < 1, a count < 1, a range outside [0, n), a pointer off 4-byte alignment, d_values off 16-byte

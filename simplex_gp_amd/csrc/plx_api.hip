@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace plx {
@@ -950,141 +951,130 @@ int plx_apply_backward_f64(plx_lattice *L, const double *d_g, const double *d_sr
                                       d_grad_x, d_grad_src, s);
 }
 
-// ---- the float64 position gradient of the rectangular product, one side per call (kernels: plx_rows_backward_f64.hip) ----
+// ---- the position gradient of the rectangular product, one side per call, in fp32 and in float64 (kernels:
+// plx_rows_backward_kernels.h; what the types differ in here: RowsBackwardHost<T>, plx_internal.h) --------------------------
+extern "C++" {      // one body per call for both types; the six entry points below forward to them
 
 // Everything a one-sided call checks before any GPU work: the pointer checks of check_backward_f64 and the counts, which
 // need no lattice, first; then the built lattice, the column limit on the row stride, the ranges, the build and the sizes.
-static int check_backward_rows_f64(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
-                                   bool last_out_optional, int nrhs, const int64_t (*ranges)[2], int n_ranges, const char *who)
+template <typename T>
+static int check_backward_rows(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
+                               bool last_out_optional, int nrhs, const int64_t (*ranges)[2], int n_ranges, const char *who)
 {
-    PLX_TRY(check_backward_ptrs(L, in, n_in, out, n_out, last_out_optional, nrhs, who));
+    using S = RowsBackwardHost<T>;
+    PLX_TRY(check_backward_ptrs(L, in, n_in, out, n_out, last_out_optional, nrhs, who, std::is_same_v<T, double>));
     for (int r = 0; r < n_ranges; ++r)
         if (ranges[r][1] < 1) { set_error("%s: a row count of %lld must be positive", who, (long long)ranges[r][1]); return PLX_ERR_INVALID; }
     if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
-    const int64_t cols = (int64_t)nrhs * (1 + L->d), stride = (cols + 1) & ~1ll;
-    if (stride > kBackwardF64MaxCols) {
-        set_error("%s: nrhs = %d, d = %d is a row of %lld doubles; the on-chip row of the contraction holds up to %d", who, nrhs,
-                  L->d, (long long)stride, kBackwardF64MaxCols);
+    const int64_t cols = (int64_t)nrhs * (1 + L->d), stride = (cols + (S::kPack - 1)) & ~(int64_t)(S::kPack - 1);
+    if (stride > S::kMaxCols) {
+        set_error("%s: nrhs = %d, d = %d is a row of %lld %s; the on-chip row of the contraction holds up to %d", who, nrhs, L->d,
+                  (long long)stride, S::kPlural, S::kMaxCols);
         return PLX_ERR_INVALID;
     }
     for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_range(L, ranges[r][0], ranges[r][1], who));
-    PLX_TRY(check_plain_build(L, "the float64 row-range gradient is", who));
+    PLX_TRY(check_plain_build(L, S::kGradientIs, who));
     for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_size(L, (int)stride, ranges[r][1], "rows", who));
     return PLX_OK;
 }
 
-int plx_backward_splat_rows_f64(plx_lattice *L, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_x, int nrhs,
-                                double *d_values, void *stream)
+template <typename T>
+static int backward_splat_rows_entry(const char *who, plx_lattice *L, const T *d_a, int64_t a_begin, int64_t a_count, const T *d_x,
+                                     int nrhs, T *d_values, void *stream)
 {
     EntryScope sc(L, stream);
     const void *in[] = {d_a, d_x}, *out[] = {d_values};
     const int64_t ranges[][2] = {{a_begin, a_count}};
-    PLX_TRY(check_backward_rows_f64(L, in, 2, out, 1, false, nrhs, ranges, 1, "plx_backward_splat_rows_f64"));
-    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_splat_rows_f64"));
+    PLX_TRY(check_backward_rows<T>(L, in, 2, out, 1, false, nrhs, ranges, 1, who));
+    PLX_TRY(check_values_aligned(d_values, 2, who));
     DeviceGuard g(L->device);
-    return backward_splat_rows_f64_impl(L, d_a, a_begin, a_count, d_x, nrhs, d_values, (hipStream_t)stream);
+    return backward_splat_rows_impl<T>(L, d_a, a_begin, a_count, d_x, nrhs, d_values, (hipStream_t)stream);
+}
+
+template <typename T>
+static int backward_contract_rows_entry(const char *who, plx_lattice *L, const T *d_values, const T *d_b, int64_t b_begin,
+                                        int64_t b_count, const T *d_x, int nrhs, T *d_grad_x, T *d_filtered, void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_values, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
+    const int64_t ranges[][2] = {{b_begin, b_count}};
+    PLX_TRY(check_backward_rows<T>(L, in, 3, out, 2, true, nrhs, ranges, 1, who));
+    PLX_TRY(check_values_aligned(d_values, 2, who));
+    DeviceGuard g(L->device);
+    return backward_contract_rows_impl<T>(L, d_values, d_b, b_begin, b_count, d_x, nrhs, d_grad_x, d_filtered, (hipStream_t)stream);
+}
+
+// the two around the blur of the type, on the workspace of plx_apply_rows (float) or of plx_apply_f64 (double)
+template <typename T>
+static int apply_backward_rows_entry(const char *who, plx_lattice *L, const T *d_a, int64_t a_begin, int64_t a_count, const T *d_b,
+                                     int64_t b_begin, int64_t b_count, const T *d_x, int nrhs, T *d_grad_x, T *d_filtered,
+                                     void *stream)
+{
+    EntryScope sc(L, stream);
+    const void *in[] = {d_a, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
+    const int64_t ranges[][2] = {{a_begin, a_count}, {b_begin, b_count}};
+    PLX_TRY(check_backward_rows<T>(L, in, 3, out, 2, true, nrhs, ranges, 2, who));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int H = nrhs * (1 + L->d);
+    const size_t bytes = (size_t)L->m * RowsBackwardHost<T>::stride(H) * sizeof(T);
+    constexpr bool f64 = std::is_same_v<T, double>;
+    DevBuf &work_a = f64 ? L->val64_a : L->val_a, &work_b = f64 ? L->val64_b : L->val_b;
+    PLX_TRY(ensure(work_a, bytes));
+    PLX_TRY(ensure(work_b, bytes));
+    T *va = work_a.template as<T>(), *vb = work_b.template as<T>();
+    PLX_TRY(backward_rows_tables<T>(L, a_begin, a_count, b_begin, b_count, s));
+    PLX_TRY(backward_splat_rows_impl<T>(L, d_a, a_begin, a_count, d_x, nrhs, va, s));
+    int in_b = 0;
+    if constexpr (f64) {
+        PLX_TRY(blur_f64_impl(L, va, vb, H, &in_b, s));
+    } else {
+        PLX_TRY(blur_impl(L, va, vb, H, &in_b, s));
+    }
+    return backward_contract_rows_impl<T>(L, in_b ? vb : va, d_b, b_begin, b_count, d_x, nrhs, d_grad_x, d_filtered, s);
+}
+
+}  // extern "C++"
+
+int plx_backward_splat_rows_f64(plx_lattice *L, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_x, int nrhs,
+                                double *d_values, void *stream)
+{
+    return backward_splat_rows_entry<double>("plx_backward_splat_rows_f64", L, d_a, a_begin, a_count, d_x, nrhs, d_values, stream);
 }
 
 int plx_backward_contract_rows_f64(plx_lattice *L, const double *d_values, const double *d_b, int64_t b_begin, int64_t b_count,
                                    const double *d_x, int nrhs, double *d_grad_x, double *d_filtered, void *stream)
 {
-    EntryScope sc(L, stream);
-    const void *in[] = {d_values, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
-    const int64_t ranges[][2] = {{b_begin, b_count}};
-    PLX_TRY(check_backward_rows_f64(L, in, 3, out, 2, true, nrhs, ranges, 1, "plx_backward_contract_rows_f64"));
-    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_contract_rows_f64"));
-    DeviceGuard g(L->device);
-    return backward_contract_rows_f64_impl(L, d_values, d_b, b_begin, b_count, d_x, nrhs, d_grad_x, d_filtered,
-                                           (hipStream_t)stream);
+    return backward_contract_rows_entry<double>("plx_backward_contract_rows_f64", L, d_values, d_b, b_begin, b_count, d_x, nrhs,
+                                                d_grad_x, d_filtered, stream);
 }
 
 int plx_apply_backward_rows_f64(plx_lattice *L, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_b,
                                 int64_t b_begin, int64_t b_count, const double *d_x, int nrhs, double *d_grad_x,
                                 double *d_filtered, void *stream)
 {
-    EntryScope sc(L, stream);
-    const void *in[] = {d_a, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
-    const int64_t ranges[][2] = {{a_begin, a_count}, {b_begin, b_count}};
-    PLX_TRY(check_backward_rows_f64(L, in, 3, out, 2, true, nrhs, ranges, 2, "plx_apply_backward_rows_f64"));
-    DeviceGuard g(L->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int H = nrhs * (1 + L->d);
-    const size_t bytes = (size_t)L->m * values_stride_f64(H) * 8;
-    PLX_TRY(ensure(L->val64_a, bytes));      // the workspace of plx_apply_f64
-    PLX_TRY(ensure(L->val64_b, bytes));
-    PLX_TRY(backward_rows_f64_tables(L, a_begin, a_count, b_begin, b_count, s));
-    PLX_TRY(backward_splat_rows_f64_impl(L, d_a, a_begin, a_count, d_x, nrhs, L->val64_a.as<double>(), s));
-    int in_b = 0;
-    PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), H, &in_b, s));
-    return backward_contract_rows_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), d_b, b_begin, b_count,
-                                           d_x, nrhs, d_grad_x, d_filtered, s);
-}
-
-// ---- the fp32 position gradient of the rectangular product, one side per call (kernels: plx_rows_backward.hip) ----------
-
-// check_backward_rows_f64 for buffers of floats: the row stride is nrhs (1 + d) rounded up to 4, under kBackwardRowsMaxCols.
-static int check_backward_rows(const plx_lattice *L, const void *const *in, int n_in, const void *const *out, int n_out,
-                               bool last_out_optional, int nrhs, const int64_t (*ranges)[2], int n_ranges, const char *who)
-{
-    PLX_TRY(check_backward_ptrs(L, in, n_in, out, n_out, last_out_optional, nrhs, who, false));
-    for (int r = 0; r < n_ranges; ++r)
-        if (ranges[r][1] < 1) { set_error("%s: a row count of %lld must be positive", who, (long long)ranges[r][1]); return PLX_ERR_INVALID; }
-    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
-    const int64_t cols = (int64_t)nrhs * (1 + L->d), stride = (cols + 3) & ~3ll;
-    if (stride > kBackwardRowsMaxCols) {
-        set_error("%s: nrhs = %d, d = %d is a row of %lld floats; the on-chip row of the contraction holds up to %d", who, nrhs,
-                  L->d, (long long)stride, kBackwardRowsMaxCols);
-        return PLX_ERR_INVALID;
-    }
-    for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_range(L, ranges[r][0], ranges[r][1], who));
-    PLX_TRY(check_plain_build(L, "the row-range gradient is", who));
-    for (int r = 0; r < n_ranges; ++r) PLX_TRY(check_size(L, (int)stride, ranges[r][1], "rows", who));
-    return PLX_OK;
+    return apply_backward_rows_entry<double>("plx_apply_backward_rows_f64", L, d_a, a_begin, a_count, d_b, b_begin, b_count, d_x,
+                                             nrhs, d_grad_x, d_filtered, stream);
 }
 
 int plx_backward_splat_rows(plx_lattice *L, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_x, int nrhs,
                             float *d_values, void *stream)
 {
-    EntryScope sc(L, stream);
-    const void *in[] = {d_a, d_x}, *out[] = {d_values};
-    const int64_t ranges[][2] = {{a_begin, a_count}};
-    PLX_TRY(check_backward_rows(L, in, 2, out, 1, false, nrhs, ranges, 1, "plx_backward_splat_rows"));
-    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_splat_rows"));
-    DeviceGuard g(L->device);
-    return backward_splat_rows_impl(L, d_a, a_begin, a_count, d_x, nrhs, d_values, (hipStream_t)stream);
+    return backward_splat_rows_entry<float>("plx_backward_splat_rows", L, d_a, a_begin, a_count, d_x, nrhs, d_values, stream);
 }
 
 int plx_backward_contract_rows(plx_lattice *L, const float *d_values, const float *d_b, int64_t b_begin, int64_t b_count,
                                const float *d_x, int nrhs, float *d_grad_x, float *d_filtered, void *stream)
 {
-    EntryScope sc(L, stream);
-    const void *in[] = {d_values, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
-    const int64_t ranges[][2] = {{b_begin, b_count}};
-    PLX_TRY(check_backward_rows(L, in, 3, out, 2, true, nrhs, ranges, 1, "plx_backward_contract_rows"));
-    PLX_TRY(check_values_aligned(d_values, 2, "plx_backward_contract_rows"));
-    DeviceGuard g(L->device);
-    return backward_contract_rows_impl(L, d_values, d_b, b_begin, b_count, d_x, nrhs, d_grad_x, d_filtered, (hipStream_t)stream);
+    return backward_contract_rows_entry<float>("plx_backward_contract_rows", L, d_values, d_b, b_begin, b_count, d_x, nrhs, d_grad_x,
+                                               d_filtered, stream);
 }
 
 int plx_apply_backward_rows(plx_lattice *L, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_b, int64_t b_begin,
                             int64_t b_count, const float *d_x, int nrhs, float *d_grad_x, float *d_filtered, void *stream)
 {
-    EntryScope sc(L, stream);
-    const void *in[] = {d_a, d_b, d_x}, *out[] = {d_grad_x, d_filtered};
-    const int64_t ranges[][2] = {{a_begin, a_count}, {b_begin, b_count}};
-    PLX_TRY(check_backward_rows(L, in, 3, out, 2, true, nrhs, ranges, 2, "plx_apply_backward_rows"));
-    DeviceGuard g(L->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int H = nrhs * (1 + L->d);
-    const size_t bytes = (size_t)L->m * values_stride(H) * 4;
-    PLX_TRY(ensure(L->val_a, bytes));      // the workspace of plx_apply_rows
-    PLX_TRY(ensure(L->val_b, bytes));
-    PLX_TRY(backward_rows_tables(L, a_begin, a_count, b_begin, b_count, s));
-    PLX_TRY(backward_splat_rows_impl(L, d_a, a_begin, a_count, d_x, nrhs, L->val_a.as<float>(), s));
-    int in_b = 0;
-    PLX_TRY(blur_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), H, &in_b, s));
-    return backward_contract_rows_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), d_b, b_begin, b_count, d_x, nrhs,
-                                       d_grad_x, d_filtered, s);
+    return apply_backward_rows_entry<float>("plx_apply_backward_rows", L, d_a, a_begin, a_count, d_b, b_begin, b_count, d_x, nrhs,
+                                            d_grad_x, d_filtered, stream);
 }
 
 int plx_apply_backward(plx_lattice *L, const float *d_g, const float *d_src, const float *d_ref, int nrhs,

@@ -32,7 +32,8 @@
 namespace plx {
 
 // (the stack element and its vertex sum -- StackCol64, stack_col64, stack_elem64, stack_vertex_sum64 -- are in plx_kernels.h,
-// shared with plx_rows_backward_f64.hip)
+// shared with the trait of plx_rows_backward_f64.hip; the one-sided form's kernels are the templates of
+// plx_rows_backward_kernels.h, this file's have the same skeleton over two inputs and the point permutation)
 __global__ __launch_bounds__(kBlock) void f64_backward_splat_chunk_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
                                                                           const float *__restrict__ w, const double *__restrict__ g,
                                                                           const double *__restrict__ src, const double *__restrict__ x,
@@ -148,9 +149,9 @@ int backward_splat_f64_impl(plx_lattice *L, const double *d_g, const double *d_s
     const int *ptr = L->row_ptr.as<int>(), *row = L->csr_row.as<int>();
     const float *w = L->csr_w.as<float>();
     double2 *v2 = reinterpret_cast<double2 *>(d_values);
-    if (nch <= kF64ChunkMax) {
+    if (nch <= kChunkGroupMax) {
         L->kn_f64_splat = "f64_backward_splat_chunk_kernel";
-        const int shift = f64_group_shift(nch);
+        const int shift = chunk_group_shift(nch);
         const int grid = ceil_div((int64_t)m << shift, kBlock);
         f64_backward_splat_chunk_kernel<<<grid, kBlock, 0, stream>>>(ptr, row, w, d_g, d_src, d_x, nrhs, d, nch, shift, m, v2);
     } else {
@@ -171,9 +172,9 @@ int backward_contract_f64_impl(plx_lattice *L, const double *d_values, const dou
     const int *evid = L->evid.as<int>();
     const float *ew = L->ew.as<float>();
     const double2 *v2 = reinterpret_cast<const double2 *>(d_values);
-    if (nch <= kF64ChunkMax) {
+    if (nch <= kChunkGroupMax) {
         L->kn_f64_slice = "f64_backward_contract_chunk_kernel";
-        const int shift = f64_group_shift(nch);
+        const int shift = chunk_group_shift(nch);
         const int grid = ceil_div((int64_t)n << shift, kBlock);
         dispatch_d1(d1, [&](auto D1) {
             f64_backward_contract_chunk_kernel<decltype(D1)::value><<<grid, kBlock, 0, stream>>>(

@@ -315,8 +315,8 @@ int affine_f64_dot_rows(const plx_lattice *L, int vd)
 {
     if (vd == 1) return ceil_div(L->n, kBlock);
     const int nch = values_stride_f64(vd) / 2;
-    if (nch > kF64ChunkMax) return 0;
-    return ceil_div((int64_t)L->n << f64_group_shift(nch), kBlock);
+    if (nch > kChunkGroupMax) return 0;
+    return ceil_div((int64_t)L->n << chunk_group_shift(nch), kBlock);
 }
 
 template <bool VEC>
@@ -324,7 +324,7 @@ static void launch_affine_chunk_f64(plx_lattice *L, const double2 *v2, int vd, i
                                     const double *d_ss, double *d_out, double *d_partial, hipStream_t stream)
 {
     const int n = (int)L->n, d1 = L->d + 1;
-    const int shift = f64_group_shift(nch);
+    const int shift = chunk_group_shift(nch);
     const int grid = ceil_div((int64_t)n << shift, kBlock);
     const uint32_t *perm = L->perm.as<uint32_t>();
     const int *evid = L->evid.as<int>();
@@ -360,7 +360,7 @@ int slice_affine_f64_impl(plx_lattice *L, const double *d_values, int vd, const 
             f64_affine_v1_kernel<decltype(D1)::value><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, d_values, denom,
                                                                                    d_src, d_ss, d_out, d_partial);
         });
-    } else if (nch <= kF64ChunkMax) {
+    } else if (nch <= kChunkGroupMax) {
         L->kn_f64_slice = "f64_affine_chunk_kernel";
         if (vec) launch_affine_chunk_f64<true>(L, v2, vd, nch, denom, d_src, d_ss, d_out, d_partial, stream);
         else launch_affine_chunk_f64<false>(L, v2, vd, nch, denom, d_src, d_ss, d_out, d_partial, stream);

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void f64_slice_wide_kernel(const uint32_t *
         f64_store_chunk<VEC>(out, row, vd, ch, f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom));
 }
 
-// ---- launch side (kF64ChunkMax / f64_vec_ok / f64_group_shift: plx_kernels.h) -----------------------------------------------
+// ---- launch side (kChunkGroupMax / f64_vec_ok / chunk_group_shift: plx_kernels.h) -----------------------------------------------
 // The vertex-sorted corners of the current build and the first corner of every vertex (ensure_csr + its row pointer):
 // built by the first fp64 splat after a build, kept until the next one.
 static int ensure_f64_tables(plx_lattice *L, hipStream_t stream)
@@ -218,9 +218,9 @@ int splat_f64_impl(plx_lattice *L, const double *d_src, int vd, double *d_values
     if (vd == 1) {
         L->kn_f64_splat = "f64_splat_v1_kernel";
         f64_splat_v1_kernel<<<ceil_div(m, kBlock), kBlock, 0, stream>>>(ptr, row, w, d_src, m, d_values);
-    } else if (nch <= kF64ChunkMax) {
+    } else if (nch <= kChunkGroupMax) {
         L->kn_f64_splat = "f64_splat_chunk_kernel";
-        const int shift = f64_group_shift(nch);
+        const int shift = chunk_group_shift(nch);
         const int grid = ceil_div((int64_t)m << shift, kBlock);
         if (vec) f64_splat_chunk_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v2);
         else f64_splat_chunk_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v2);
@@ -282,7 +282,7 @@ static void launch_slice_chunk_f64(plx_lattice *L, const double2 *v2, int vd, in
                                    hipStream_t stream)
 {
     const int n = (int)L->n, d1 = L->d + 1;
-    const int shift = f64_group_shift(nch);
+    const int shift = chunk_group_shift(nch);
     const int grid = ceil_div((int64_t)n << shift, kBlock);
     const uint32_t *perm = L->perm.as<uint32_t>();
     const int *evid = L->evid.as<int>();
@@ -309,7 +309,7 @@ int slice_f64_impl(plx_lattice *L, const double *d_values, int vd, double *d_out
             f64_slice_v1_kernel<decltype(D1)::value><<<grid, kBlock, 0, stream>>>(perm, evid, ew, n, d1, d_values,
                                                                                   denom, d_out);
         });
-    } else if (nch <= kF64ChunkMax) {
+    } else if (nch <= kChunkGroupMax) {
         L->kn_f64_slice = "f64_slice_chunk_kernel";
         if (vec) launch_slice_chunk_f64<true>(L, v2, vd, nch, denom, d_out, stream);
         else launch_slice_chunk_f64<false>(L, v2, vd, nch, denom, d_out, stream);

@@ -423,25 +423,6 @@ int backward_splat_f64_impl(plx_lattice *L, const double *d_g, const double *d_s
                             double *d_values, hipStream_t stream);
 int backward_contract_f64_impl(plx_lattice *L, const double *d_values, const double *d_g, const double *d_src,
                                const double *d_x, int nrhs, double *d_grad_x, double *d_grad_src, hipStream_t stream);
-// plx_rows_backward_f64.hip: the one-sided float64 position gradient of the rectangular product -- the splat of the half
-// stack [ a | a (x) x ] (nrhs (1 + d) columns) over the rows of a, and the slice with the contraction against b fused over
-// the rows of b (arguments checked by the entry points); d_x is [n][d], all stacked points.  backward_rows_f64_tables:
-// both range tables of a call before its first launch.  The column limit is kBackwardF64MaxCols on the row stride.
-int backward_rows_f64_tables(plx_lattice *L, int64_t a_begin, int64_t a_count, int64_t b_begin, int64_t b_count,
-                             hipStream_t stream);
-int backward_splat_rows_f64_impl(plx_lattice *L, const double *d_a, int64_t a_begin, int64_t a_count, const double *d_x, int nrhs,
-                                 double *d_values, hipStream_t stream);
-int backward_contract_rows_f64_impl(plx_lattice *L, const double *d_values, const double *d_b, int64_t b_begin, int64_t b_count,
-                                    const double *d_x, int nrhs, double *d_grad_x, double *d_filtered, hipStream_t stream);
-// plx_rows_backward.hip: the same one-sided gradient in fp32 on whole float4 chunks (stride = values_stride(nrhs (1 + d))),
-// over the same range tables, around blur_impl.  kBackwardRowsMaxCols: the widest row stride the on-chip row of the
-// contraction holds (4 rows of floats in 64 KiB of LDS).
-constexpr int kBackwardRowsMaxCols = 4096;
-int backward_rows_tables(plx_lattice *L, int64_t a_begin, int64_t a_count, int64_t b_begin, int64_t b_count, hipStream_t stream);
-int backward_splat_rows_impl(plx_lattice *L, const float *d_a, int64_t a_begin, int64_t a_count, const float *d_x, int nrhs,
-                             float *d_values, hipStream_t stream);
-int backward_contract_rows_impl(plx_lattice *L, const float *d_values, const float *d_b, int64_t b_begin, int64_t b_count,
-                                const float *d_x, int nrhs, float *d_grad_x, float *d_filtered, hipStream_t stream);
 // plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
 int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,
@@ -467,6 +448,35 @@ const Tunable *tunables();
 inline int values_stride(int vd) { return vd == 1 ? 1 : (vd + 3) & ~3; }
 // ... and in doubles (the float64 product): 1, else the column count rounded up to 2
 inline int values_stride_f64(int vd) { return vd == 1 ? 1 : (vd + 1) & ~1; }
+
+// plx_rows_backward_kernels.h, instantiated by plx_rows_backward.hip (float) and plx_rows_backward_f64.hip (double): the
+// one-sided position gradient of the rectangular product -- the splat of the half stack [ a | a (x) x ] (nrhs (1 + d)
+// columns) over the rows of a, and the slice with the contraction against b fused over the rows of b (arguments checked by
+// the entry points); d_x is [n][d], all stacked points, and the tables are the range tables of plx_rows.hip.
+// backward_rows_tables: both range tables of a call before its first launch.  The blur between the two is blur_impl or
+// blur_f64_impl.  RowsBackwardHost<T>: what the two types differ in outside the kernels -- the elements of a 16-byte chunk,
+// the row stride, the widest stride the on-chip row of the contraction holds (4 rows in 64 KiB of LDS) and the words of the
+// refusals.
+constexpr int kBackwardRowsMaxCols = 4096;
+template <typename T> struct RowsBackwardHost;
+template <> struct RowsBackwardHost<float> {
+    static constexpr int kPack = 4, kMaxCols = kBackwardRowsMaxCols;
+    static constexpr const char *kPlural = "floats", *kGradientIs = "the row-range gradient is";
+    static int stride(int vd) { return values_stride(vd); }
+};
+template <> struct RowsBackwardHost<double> {
+    static constexpr int kPack = 2, kMaxCols = kBackwardF64MaxCols;
+    static constexpr const char *kPlural = "doubles", *kGradientIs = "the float64 row-range gradient is";
+    static int stride(int vd) { return values_stride_f64(vd); }
+};
+template <typename T>
+int backward_rows_tables(plx_lattice *L, int64_t a_begin, int64_t a_count, int64_t b_begin, int64_t b_count, hipStream_t stream);
+template <typename T>
+int backward_splat_rows_impl(plx_lattice *L, const T *d_a, int64_t a_begin, int64_t a_count, const T *d_x, int nrhs, T *d_values,
+                             hipStream_t stream);
+template <typename T>
+int backward_contract_rows_impl(plx_lattice *L, const T *d_values, const T *d_b, int64_t b_begin, int64_t b_count, const T *d_x,
+                                int nrhs, T *d_grad_x, T *d_filtered, hipStream_t stream);
 
 // contiguous near-equal row blocks: the first n % shards blocks get one extra row
 inline void shard_range(int64_t n, int shards, int index, int64_t *lo, int64_t *hi)

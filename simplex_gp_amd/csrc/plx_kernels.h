@@ -1,6 +1,7 @@
 // plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
 // plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip,
-// plx_rows_f64.hip, plx_backward_f64.hip, plx_rows_backward_f64.hip, plx_rows_backward.hip).  Not part of the C ABI.
+// plx_rows_f64.hip, plx_backward_f64.hip, and through plx_rows_backward_kernels.h plx_rows_backward.hip and
+// plx_rows_backward_f64.hip).  Not part of the C ABI.
 //
 // Reference: cpp/permutohedral.h ("h") splat value accumulation h:478-479,
 // blur h:513-572, slice h:497-510.  The reference's CUDA path does the splat
@@ -267,9 +268,11 @@ __device__ __forceinline__ float4 rows_filtered_chunk(const int *__restrict__ ev
     }
 }
 
-constexpr int kF64ChunkMax = 64;      // chunks one lane group can cover: a group never spans two waves
 static inline bool f64_vec_ok(const void *p, int vd) { return (vd & 1) == 0 && ((uintptr_t)p & 15) == 0; }
-static inline int f64_group_shift(int nch)
+// The chunk shape of the float64 kernels and of both row-range gradients: a group of 2^shift >= nch lanes per row, one lane
+// per 16-byte chunk (float4 or double2), up to kChunkGroupMax chunks: a group never spans two waves.
+constexpr int kChunkGroupMax = 64;
+static inline int chunk_group_shift(int nch)
 {
     int s = 0;
     while ((1 << s) < nch) ++s;

@@ -269,7 +269,8 @@ __global__ __launch_bounds__(kBlock) void rows_splat_wide_kernel(const int *__re
 }
 
 // ---- slice ---------------------------------------------------------------------------------------------------------
-// (rows_point_sum and rows_filtered_chunk, the sums of a filtered chunk: plx_kernels.h, shared with plx_rows_backward.hip)
+// (rows_point_sum and rows_filtered_chunk, the sums of a filtered chunk: plx_kernels.h, shared with the fp32 trait of
+// plx_rows_backward_kernels.h in plx_rows_backward.hip)
 __global__ __launch_bounds__(kBlock) void rows_slice_v1_kernel(const int *__restrict__ pos, const int *__restrict__ prow,
                                                                const int *__restrict__ evid, const float *__restrict__ ew,
                                                                int n, int d1, int count, const float *__restrict__ values,

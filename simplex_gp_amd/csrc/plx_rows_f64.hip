@@ -148,9 +148,9 @@ int splat_rows_f64_impl(plx_lattice *L, const double *d_src, int64_t begin, int6
     if (vd == 1) {
         L->kn_rows64_splat = "rows64_splat_v1_kernel";
         rows64_splat_v1_kernel<<<ceil_div(m, kBlock), kBlock, 0, stream>>>(ptr, row, w, d_src, m, d_values);
-    } else if (nch <= kF64ChunkMax) {
+    } else if (nch <= kChunkGroupMax) {
         L->kn_rows64_splat = "rows64_splat_chunk_kernel";
-        const int shift = f64_group_shift(nch);
+        const int shift = chunk_group_shift(nch);
         const int grid = ceil_div((int64_t)m << shift, kBlock);
         if (vec) rows64_splat_chunk_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v2);
         else rows64_splat_chunk_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v2);
@@ -169,7 +169,7 @@ static void launch_slice_chunk_rows64(plx_lattice *L, const plx_lattice::RowsRan
                                       double denom, double *d_out, hipStream_t stream)
 {
     const int n = (int)L->n, d1 = L->d + 1, count = (int)r->count;
-    const int shift = f64_group_shift(nch);
+    const int shift = chunk_group_shift(nch);
     const int grid = ceil_div((int64_t)count << shift, kBlock);
     const int *pos = r->pos.as<int>(), *prow = r->prow.as<int>();
     const int *evid = L->evid.as<int>();
@@ -199,7 +199,7 @@ int slice_rows_f64_impl(plx_lattice *L, const double *d_values, int vd, int64_t 
             rows64_slice_v1_kernel<decltype(D1)::value><<<grid, kBlock, 0, stream>>>(pos, prow, evid, ew, n, d1, (int)count,
                                                                                      d_values, denom, d_out);
         });
-    } else if (nch <= kF64ChunkMax) {
+    } else if (nch <= kChunkGroupMax) {
         L->kn_rows64_slice = "rows64_slice_chunk_kernel";
         if (vec) launch_slice_chunk_rows64<true>(L, r, v2, vd, nch, denom, d_out, stream);
         else launch_slice_chunk_rows64<false>(L, r, v2, vd, nch, denom, d_out, stream);

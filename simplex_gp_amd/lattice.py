@@ -741,32 +741,38 @@ class Lattice:
         Returns (grad_x [len(b), d], filtered [len(b), nrhs] or None); filtered is the derivative-tap filter of `a` on the
         rows of b.  (a = grad_out on the out rows, b = src on the source rows) is the gradient of the source rows'
         positions, (a = src, b = grad_out) that of the out rows'.  float64 CUDA tensors only: there is no fp32 form."""
+        return self._apply_backward_rows(torch.float64, "plx_apply_backward_rows_f64", "apply_backward_rows has no fp32 form",
+                                         a, a_begin, b, b_begin, x, want_filtered)
+
+    def _apply_backward_rows(self, dtype, symbol, who, a, a_begin, b, b_begin, x, want_filtered):
+        """The body of apply_backward_rows (float64) and apply_backward_rows_f32 (float32): `symbol` is the library's call
+        for `dtype`, `who` opens the refusal of any other dtype with the public method's name."""
         for t, name in ((a, "a"), (b, "b"), (x, "x")):
             if not isinstance(t, torch.Tensor):
                 raise TypeError(f"{name} must be a torch.Tensor")
-        if {a.dtype, b.dtype, x.dtype} != {torch.float64}:
-            raise TypeError("apply_backward_rows has no fp32 form: a, b and x must all be float64, got "
+        if {a.dtype, b.dtype, x.dtype} != {dtype}:
+            raise TypeError(f"{who}: a, b and x must all be {str(dtype).split('.')[-1]}, got "
                             f"{a.dtype}, {b.dtype} and {x.dtype}")
+        f64_ok = dtype == torch.float64
         for t, name in ((a, "a"), (b, "b"), (x, "x")):
-            _check_f32_cuda(t, name, f64_ok=True)
-        a, b, x = a.contiguous(), b.contiguous(), self._src(x, self.n, f64_ok=True)
+            _check_f32_cuda(t, name, f64_ok=f64_ok)
+        a, b, x = a.contiguous(), b.contiguous(), self._src(x, self.n, f64_ok=f64_ok)
         ab, ac = self._rows(a_begin, a.shape[0])
         bb, bc = self._rows(b_begin, b.shape[0])
         if a.shape[1] != b.shape[1] or x.shape[1] != self.d:
             raise ValueError(f"Incompatible shapes {tuple(a.shape)}, {tuple(b.shape)}, {tuple(x.shape)}")
         nrhs = a.shape[1]
-        grad_x = torch.empty((bc, self.d), dtype=torch.float64, device=self.device)
-        filtered = torch.empty((bc, nrhs), dtype=torch.float64, device=self.device) if want_filtered else None
+        grad_x = torch.empty((bc, self.d), dtype=dtype, device=self.device)
+        filtered = torch.empty((bc, nrhs), dtype=dtype, device=self.device) if want_filtered else None
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_apply_backward_rows_f64(self._h, ctypes.c_void_p(a.data_ptr()), ab, ac,
-                                                      ctypes.c_void_p(b.data_ptr()), bb, bc, ctypes.c_void_p(x.data_ptr()),
-                                                      nrhs, ctypes.c_void_p(grad_x.data_ptr()),
-                                                      ctypes.c_void_p(filtered.data_ptr()) if want_filtered else None,
-                                                      _stream_ptr(self.device))
-        nv.check(rc, "plx_apply_backward_rows_f64")
+            rc = getattr(nv.lib(), symbol)(self._h, ctypes.c_void_p(a.data_ptr()), ab, ac, ctypes.c_void_p(b.data_ptr()), bb, bc,
+                                           ctypes.c_void_p(x.data_ptr()), nrhs, ctypes.c_void_p(grad_x.data_ptr()),
+                                           ctypes.c_void_p(filtered.data_ptr()) if want_filtered else None,
+                                           _stream_ptr(self.device))
+        nv.check(rc, symbol)
         return grad_x, filtered
 
-    BACKWARD_ROWS_MAX_STRIDE = 4096          # kBackwardRowsMaxCols of plx_rows_backward.hip, on the fp32 row stride
+    BACKWARD_ROWS_MAX_STRIDE = 4096          # kBackwardRowsMaxCols on the row stride of the fp32 half stack
 
     @staticmethod
     def backward_rows_ok(nrhs, d):
@@ -778,30 +784,8 @@ class Lattice:
         """The fp32 form of apply_backward_rows (plx_apply_backward_rows), with its return convention: the lattice is built
         with the DERIVATIVE taps on `x` [n, d].  float32 CUDA tensors only; the name is its own because apply_backward_rows
         refuses every float32 tensor and does not dispatch on dtype."""
-        for t, name in ((a, "a"), (b, "b"), (x, "x")):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{name} must be a torch.Tensor")
-        if {a.dtype, b.dtype, x.dtype} != {torch.float32}:
-            raise TypeError("apply_backward_rows_f32: a, b and x must all be float32, got "
-                            f"{a.dtype}, {b.dtype} and {x.dtype}")
-        for t, name in ((a, "a"), (b, "b"), (x, "x")):
-            _check_f32_cuda(t, name)
-        a, b, x = a.contiguous(), b.contiguous(), self._src(x, self.n)
-        ab, ac = self._rows(a_begin, a.shape[0])
-        bb, bc = self._rows(b_begin, b.shape[0])
-        if a.shape[1] != b.shape[1] or x.shape[1] != self.d:
-            raise ValueError(f"Incompatible shapes {tuple(a.shape)}, {tuple(b.shape)}, {tuple(x.shape)}")
-        nrhs = a.shape[1]
-        grad_x = torch.empty((bc, self.d), dtype=torch.float32, device=self.device)
-        filtered = torch.empty((bc, nrhs), dtype=torch.float32, device=self.device) if want_filtered else None
-        with torch.cuda.device(self.device):
-            rc = nv.lib().plx_apply_backward_rows(self._h, ctypes.c_void_p(a.data_ptr()), ab, ac,
-                                                  ctypes.c_void_p(b.data_ptr()), bb, bc, ctypes.c_void_p(x.data_ptr()),
-                                                  nrhs, ctypes.c_void_p(grad_x.data_ptr()),
-                                                  ctypes.c_void_p(filtered.data_ptr()) if want_filtered else None,
-                                                  _stream_ptr(self.device))
-        nv.check(rc, "plx_apply_backward_rows")
-        return grad_x, filtered
+        return self._apply_backward_rows(torch.float32, "plx_apply_backward_rows", "apply_backward_rows_f32",
+                                         a, a_begin, b, b_begin, x, want_filtered)
 
     # -- introspection (parity tests) --------------------------------------
     def export(self, which):

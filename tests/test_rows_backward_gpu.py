@@ -516,7 +516,7 @@ def test_every_new_kernel_was_launched():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     text = open(os.path.join(root, "simplex_gp_amd", "csrc", "plx_rows_backward.hip")).read()
     literals = set()
-    for stmt in re.finditer(r"\bkn_rows_(?:splat|slice)\s*=([^;]*);", text):
+    for stmt in re.finditer(r"\bk(?:Splat|Contract)(?:Chunk|Wide)\s*=([^;]*);", text):
         literals.update(re.findall(r'"([^"]*)"', stmt.group(1)))
     assert literals == set(CHUNK + WIDE), literals
     assert REACHED == literals, sorted(literals - REACHED)
