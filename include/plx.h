@@ -416,6 +416,49 @@ int plx_apply_affine_sym_f64(plx_lattice *lat, const double *d_src, int vd, doub
 int plx_last_sym_f64_kernels(const plx_lattice *lat, char *buf, int cap);
 
 /*
+ * The transposed and the symmetrised fp32 products (callers detect them by symbol; the version string is unchanged): the
+ * block above in the precision of plx_apply.  The plain fp32 blur picks among ten kernel families, some with two axes per
+ * launch; these calls run ONE family whatever the shape:
+ *   plx_blur_t            axes d .. 0 with mirrored taps, one launch of blur_axis_kernel (the general family of plx_blur)
+ *                         per axis: host code only.  Arguments of plx_blur; d_values and d_scratch must not overlap and are
+ *                         16-byte aligned for vd > 1.
+ *   plx_apply_t           splat -> blur_t -> slice: K^T d_src, on the workspace of plx_apply.
+ *   plx_blur_sym          0.5 (blur(values) + blur_t(values)) in d + 1 launches of blur_dual_kernel, each advancing both
+ *                         chains on separate planes; the first reads the one input plane for both, the last stores the one
+ *                         mean.  d_work: plx_blur_sym_work_floats(lat, vd) floats (min(d + 1, 3) planes of
+ *                         m * plx_values_stride(vd); -1 for vd < 1 or an unbuilt lattice), 16-byte aligned for vd > 1, not
+ *                         overlapping d_values.  *d_result is set on the host, without synchronisation, to d_values or to
+ *                         a plane of d_work: where the result lies.  d_values is clobbered.
+ *   plx_apply_sym         splat -> blur_sym -> slice: K_s d_src.  Runs on the workspace of plx_apply and two further
+ *                         planes that the first such call of a width allocates (refused under stream capture, PLX_ERR_STATE;
+ *                         afterwards no call allocates or synchronises).
+ *   plx_apply_affine_sym  plx_apply_affine and plx_apply_affine_dot in one, with K_s for K: d_out = a K_s d_src + b d_src.
+ *                         d_work == NULL: the affine tail only.  d_work set (plx_affine_dot_work_floats; vd in 2..256),
+ *                         d_dot == NULL: the per-tile partial sums of the column dots <d_src, d_out> stay in d_work, in the
+ *                         layout of plx_apply_affine_dot (plx_affine_dot_tiles rows).  Both set: d_dot receives the dots.
+ *                         d_out == d_src is PLX_ERR_INVALID.
+ *   plx_last_sym_kernels  "splat=...;blur=...;slice=..." of the last such call.  These calls leave what plx_last_kernels
+ *                         reports untouched.
+ * Rows follow plx_set_row_order exactly as in plx_apply.  Refusals, before any launch: NULL pointers and vd < 1
+ * (PLX_ERR_INVALID); an unbuilt lattice, a sharded or merged one, a build that replayed "reference_growth" (its neighbour
+ * table is not symmetric) (PLX_ERR_STATE); m * stride or n * stride >= 2^31 (PLX_ERR_TOO_LARGE).
+ * Bit contracts: each chain's sums are blur_axis_kernel's (same slots, same order, same expression forms), the mean is one
+ * rounded sum and an exact halving: wherever plx_blur itself runs the general family, plx_blur_sym gives the bits of
+ * 0.5f * (plx_blur + plx_blur_t) formed by the caller; in the other families the two differ by the rounding of those
+ * families.  The staged calls give the bits of plx_apply_t and plx_apply_sym; with (a, b) = (1, 0) plx_apply_affine_sym
+ * equals plx_apply_sym as values.  No atomics: two calls with the same arguments are bit-equal.
+ * K_s is symmetric to rounding; it is NOT proven positive.
+ */
+int plx_blur_t(plx_lattice *lat, float *d_values, float *d_scratch, int vd, int *result_in_scratch, void *stream);
+int plx_apply_t(plx_lattice *lat, const float *d_src, int vd, float *d_out, void *stream);
+int64_t plx_blur_sym_work_floats(const plx_lattice *lat, int vd);
+int plx_blur_sym(plx_lattice *lat, float *d_values, float *d_work, int vd, float **d_result, void *stream);
+int plx_apply_sym(plx_lattice *lat, const float *d_src, int vd, float *d_out, void *stream);
+int plx_apply_affine_sym(plx_lattice *lat, const float *d_src, int vd, float *d_out, const float *d_scale_shift,
+                         float *d_dot, float *d_work, void *stream);
+int plx_last_sym_kernels(const plx_lattice *lat, char *buf, int cap);
+
+/*
  * The float64 position gradient (callers detect it by symbol; the version string is unchanged): plx_apply_backward with
  * every array in double, for every column count.  `lat` is built with the DERIVATIVE taps on the positions rounded to
  * float, as for every fp64 call; d_x [n][d] is the caller's FLOAT64 position matrix (not the rounded copy), d_g (the

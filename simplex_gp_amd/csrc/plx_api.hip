@@ -84,7 +84,7 @@ static std::vector<DevBuf *> all_bufs(plx_lattice *L)
             &L->head_partial, &L->tail_partial, &L->val_a, &L->val_b, &L->ssrc, &L->rec, &L->perm, &L->iota, &L->cmask, &L->cbase, &L->cids, &L->merge_slot, &L->merge_flags,
             &L->sortkey_in, &L->sortkey_out,
             &L->bc_pt, &L->bc_w, &L->srow, &L->brow_ptr, &L->brow_vid, &L->s2_idx, &L->s2_ptr, &L->s2_vid, &L->s2_wave, &L->s2_wave_v, &L->partial, &L->pair_nbr, &L->inv_perm, &L->vslot, &L->vkeys_alt, &L->vslot_alt, &L->vorder,
-            &L->rows_cnt, &L->rows_vid, &L->val64_a, &L->val64_b, &L->val64_s};
+            &L->rows_cnt, &L->rows_vid, &L->val64_a, &L->val64_b, &L->val64_s, &L->val_s};
     for (auto &r : L->rows)
         for (DevBuf *b : {&r.ptr, &r.row, &r.w, &r.pos, &r.prow}) v.push_back(b);
     return v;
@@ -806,6 +806,153 @@ int plx_last_sym_f64_kernels(const plx_lattice *L, char *buf, int cap)
 {
     if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
     snprintf(buf, (size_t)cap, "splat=%s;blur=%s;slice=%s", L->kn_sym_splat, L->kn_sym_blur, L->kn_sym_slice);
+    return PLX_OK;
+}
+
+// ---- the transposed and symmetrised fp32 products (kernels: plx_sym.hip around blur_axis_kernel of plx_blur.hip) -------
+
+// splat_impl and slice_impl name their kernels in kn_splat / kn_slice: a transposed or symmetrised fp32 call moves what it
+// launched to the kn_sym32_* fields and leaves plx_last_kernels with what the last plain call reported.  (Nothing these
+// calls run assigns kn_blur.)
+struct Sym32KernelNames {
+    plx_lattice *L;
+    const char *splat, *slice;
+    Sym32KernelNames(plx_lattice *lat, const char *blur) : L(lat), splat(lat->kn_splat), slice(lat->kn_slice)
+    {
+        L->kn_splat = L->kn_slice = "";
+        L->kn_sym32_splat = L->kn_sym32_slice = "";
+        L->kn_sym32_blur = blur;
+    }
+    ~Sym32KernelNames()
+    {
+        if (*L->kn_splat) L->kn_sym32_splat = L->kn_splat;
+        if (*L->kn_slice) L->kn_sym32_slice = L->kn_slice;
+        L->kn_splat = splat;
+        L->kn_slice = slice;
+    }
+};
+
+// Everything a transposed or symmetrised fp32 call checks before any GPU work.  `a` / `b`: the call's two buffers.
+static int check_sym32(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
+{
+    PLX_TRY(check_call(L, a, b, vd, who));
+    PLX_TRY(check_plain_build(L, "the transposed and symmetrised products are", who));
+    return check_size(L, values_stride(vd), L->n, "n", who);
+}
+
+static bool floats_overlap(const float *a, int64_t na, const float *b, int64_t nb)
+{
+    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
+
+int plx_blur_t(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *result_in_scratch, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_sym32(L, d_values, d_scratch, vd, "plx_blur_t"));
+    if (!result_in_scratch) { set_error("plx_blur_t: result_in_scratch is NULL"); return PLX_ERR_INVALID; }
+    const int64_t plane = (int64_t)L->m * values_stride(vd);
+    if (floats_overlap(d_values, plane, d_scratch, plane)) {
+        set_error("plx_blur_t: d_values and d_scratch must not overlap");
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_t"));
+    PLX_TRY(check_values_aligned(d_scratch, vd, "plx_blur_t"));
+    DeviceGuard g(L->device);
+    Sym32KernelNames kn(L, "blur_axis_kernel");
+    return blur_t_impl(L, d_values, d_scratch, vd, result_in_scratch, (hipStream_t)stream);
+}
+
+int plx_apply_t(plx_lattice *L, const float *d_src, int vd, float *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_sym32(L, d_src, d_out, vd, "plx_apply_t"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    PLX_TRY(ensure(L->val_a, (size_t)L->m * values_stride(vd) * 4));      // the workspace of plx_apply
+    PLX_TRY(ensure(L->val_b, (size_t)L->m * values_stride(vd) * 4));
+    Sym32KernelNames kn(L, "blur_axis_kernel");
+    PLX_TRY(splat_impl(L, d_src, vd, L->val_a.as<float>(), s));
+    int in_b = 0;
+    PLX_TRY(blur_t_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), vd, &in_b, s));
+    return slice_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, d_out, s);
+}
+
+int64_t plx_blur_sym_work_floats(const plx_lattice *L, int vd)
+{
+    if (!L || !L->built || vd < 1) return -1;
+    return (int64_t)blur_sym_planes(L) * L->m * values_stride(vd);
+}
+
+int plx_blur_sym(plx_lattice *L, float *d_values, float *d_work, int vd, float **d_result, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_sym32(L, d_values, d_work, vd, "plx_blur_sym"));
+    if (!d_result) { set_error("plx_blur_sym: d_result is NULL"); return PLX_ERR_INVALID; }
+    const int64_t plane = (int64_t)L->m * values_stride(vd);
+    if (floats_overlap(d_values, plane, d_work, plx_blur_sym_work_floats(L, vd))) {
+        set_error("plx_blur_sym: d_values and d_work (plx_blur_sym_work_floats) must not overlap");
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_sym"));
+    PLX_TRY(check_values_aligned(d_work, vd, "plx_blur_sym"));
+    DeviceGuard g(L->device);
+    Sym32KernelNames kn(L, "blur_dual_kernel");
+    float *planes[3] = {d_work, d_work + plane, d_work + 2 * plane};      // (the last ones unused where d + 1 < 3)
+    return blur_sym_impl(L, d_values, planes, vd, d_result, (hipStream_t)stream);
+}
+
+// splat + symmetrised blur on the lattice's fp32 workspace: val_a holds the splat, val_b and the two planes of val_s are
+// the work space; *d_blurred: the plane the slice reads
+static int splat_blur_sym(plx_lattice *L, const float *d_src, int vd, float **d_blurred, hipStream_t s)
+{
+    const size_t plane = (size_t)L->m * values_stride(vd);
+    PLX_TRY(ensure(L->val_a, plane * 4));      // the workspace of plx_apply
+    PLX_TRY(ensure(L->val_b, plane * 4));
+    PLX_TRY(ensure(L->val_s, 2 * plane * 4));
+    PLX_TRY(splat_impl(L, d_src, vd, L->val_a.as<float>(), s));
+    // the three work planes need not be contiguous here: the symmetrised blur takes them one by one
+    float *planes[3] = {L->val_b.as<float>(), L->val_s.as<float>(), L->val_s.as<float>() + plane};
+    return blur_sym_impl(L, L->val_a.as<float>(), planes, vd, d_blurred, s);
+}
+
+int plx_apply_sym(plx_lattice *L, const float *d_src, int vd, float *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_sym32(L, d_src, d_out, vd, "plx_apply_sym"));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    Sym32KernelNames kn(L, "blur_dual_kernel");
+    float *blurred = nullptr;
+    PLX_TRY(splat_blur_sym(L, d_src, vd, &blurred, s));
+    return slice_impl(L, blurred, vd, d_out, s);
+}
+
+int plx_apply_affine_sym(plx_lattice *L, const float *d_src, int vd, float *d_out, const float *d_scale_shift, float *d_dot,
+                         float *d_work, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_sym32(L, d_src, d_out, vd, "plx_apply_affine_sym"));
+    if (!d_scale_shift) { set_error("plx_apply_affine_sym: NULL scale/shift"); return PLX_ERR_INVALID; }
+    if (d_dot && !d_work) { set_error("plx_apply_affine_sym: d_dot needs d_work (plx_affine_dot_work_floats)"); return PLX_ERR_INVALID; }
+    if (d_src == d_out) { set_error("plx_apply_affine_sym: d_out must not alias d_src (rows are written in a different order)"); return PLX_ERR_INVALID; }
+    if (d_work && (vd < 2 || vd > 256)) {
+        set_error("plx_apply_affine_sym: the fused dot serves vd in 2..256, got %d (pass d_work = NULL and use plx_coldot)", vd);
+        return PLX_ERR_INVALID;
+    }
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    Sym32KernelNames kn(L, "blur_dual_kernel");
+    float *blurred = nullptr;
+    PLX_TRY(splat_blur_sym(L, d_src, vd, &blurred, s));
+    PLX_TRY(slice_impl(L, blurred, vd, d_out, s, d_scale_shift, d_src, d_work));
+    if (!d_dot) return PLX_OK;          // d_work set: the per-tile partial sums stay there (plx_cg_step_update_fused adds them up)
+    return coldot_final(d_work, affine_dot_tiles(L, vd), values_stride(vd), d_dot, s);
+}
+
+int plx_last_sym_kernels(const plx_lattice *L, char *buf, int cap)
+{
+    if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
+    snprintf(buf, (size_t)cap, "splat=%s;blur=%s;slice=%s", L->kn_sym32_splat, L->kn_sym32_blur, L->kn_sym32_slice);
     return PLX_OK;
 }
 

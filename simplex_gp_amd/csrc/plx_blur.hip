@@ -729,6 +729,19 @@ static void launch_blur_general(const V *cur, V *nxt, const int *nb, int m, int6
     }
 }
 
+// One axis through the general family with the taps given (plx_sym.hip: the transposed blur runs the axes in reverse with
+// mirrored taps).  Names no kernel: the caller reports what it launched.
+void blur_axis_general(plx_lattice *L, const float *cur, float *nxt, int axis, int vd, const TapArgs &taps, hipStream_t stream)
+{
+    const int m = (int)L->m, order = L->order;
+    const int *nb = L->nbr.as<int>() + (size_t)axis * 2 * order * L->mstride;
+    if (vd == 1)
+        launch_blur_general<float>(cur, nxt, nb, m, L->mstride, 1, order, taps, stream);
+    else
+        launch_blur_general<float4>(reinterpret_cast<const float4 *>(cur), reinterpret_cast<float4 *>(nxt), nb, m, L->mstride,
+                                    values_stride(vd) / 4, order, taps, stream);
+}
+
 int blur_impl(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *result_in_scratch,
               hipStream_t stream)
 {

@@ -309,6 +309,11 @@ struct plx_lattice {
     // blur, allocated by the first plx_apply_sym_f64 of a width, and the kernels of the last such call
     plx::DevBuf val64_s;                      // double [2][m][plx_values_stride_f64(vd)]
     const char *kn_sym_splat = "", *kn_sym_blur = "", *kn_sym_slice = "";   // plx_last_sym_f64_kernels
+
+    // ... and the fp32 ones (plx_sym.hip): the two further planes of plx_apply_sym beside val_a / val_b, allocated by the
+    // first such call of a width, and the kernels of the last transposed or symmetrised fp32 call
+    plx::DevBuf val_s;                        // float [2][m][plx_values_stride(vd)]
+    const char *kn_sym32_splat = "", *kn_sym32_blur = "", *kn_sym32_slice = "";   // plx_last_sym_kernels
 };
 
 namespace plx {
@@ -374,6 +379,16 @@ int build_blur_pairs(plx_lattice *L, hipStream_t stream);   // composite neighbo
 int ensure_blur_pairs(plx_lattice *L, hipStream_t stream);  // ... built on first use (multi-column blurs, plx_filter_onehot)
 int slice_impl(plx_lattice *L, const float *d_values, int vd, float *d_out, hipStream_t stream,
                const float *d_affine = nullptr, const float *d_src = nullptr, float *d_dot_partial = nullptr);
+// plx_blur.hip: one axis of the blur through the general family (blur_axis_kernel) with the taps given: nxt = B_axis cur
+// (cur != nxt).  Assigns no kernel name.
+void blur_axis_general(plx_lattice *L, const float *cur, float *nxt, int axis, int vd, const TapArgs &taps, hipStream_t stream);
+// plx_sym.hip: the transposed fp32 blur (axes d .. 0, mirrored taps, blur_axis_general) and the symmetrised one,
+// 0.5f (blur + blur_t) with the general family's bits, both chains advanced by each of d + 1 launches.  blur_sym_planes:
+// planes of m * stride floats the symmetrised blur needs beside d_values (1, 2 or 3 of d_work[], in that order);
+// *d_result: d_values or one of them.
+int blur_t_impl(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
+int blur_sym_planes(const plx_lattice *L);
+int blur_sym_impl(plx_lattice *L, float *d_values, float *const d_work[3], int vd, float **d_result, hipStream_t stream);
 // plx_rows.hip: splat / slice restricted to the caller's rows [begin, begin + count) (arguments checked by the entry points)
 int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t count, int vd, float *d_values,
                     hipStream_t stream);

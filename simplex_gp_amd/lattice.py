@@ -411,8 +411,9 @@ class Lattice:
 
     # -- the transposed and symmetrised float64 products (plx_*_t_f64 / plx_*_sym_f64) ------
     # K is not symmetric (the axis blurs do not commute).  K^T runs the axes in reverse with mirrored taps; K_s = (K + K^T) / 2
-    # advances both blur chains in each of its d + 1 launches.  float64 only: the fp32 blur's kernel families carry
-    # order-dependent pair stencils, so its transpose is not served.
+    # advances both blur chains in each of its d + 1 launches.  These methods are float64 only; the fp32 forms have names of
+    # their own (blur_t_f32 ... below) and run one general kernel family, since the plain fp32 blur's families carry
+    # order-dependent pair stencils.
     @staticmethod
     def _f64_only(t, name, what):
         if isinstance(t, torch.Tensor) and t.dtype != torch.float64:
@@ -495,6 +496,131 @@ class Lattice:
         """Kernels launched by the last transposed or symmetrised float64 call: {"splat": [...], "blur": [...],
         "slice": [...]}; f64_kernels() goes on naming the plain float64 stages."""
         return self._last_kernels("plx_last_sym_f64_kernels", 256)
+
+    # -- the transposed and symmetrised fp32 products (plx_blur_t / plx_blur_sym / plx_apply_t / plx_apply_sym) ------
+    # The same two operators in the precision of apply(), under names of their own (the float32 TypeErrors of the methods
+    # above stay).  They run one kernel family whatever the shape -- blur_axis_kernel for K^T, blur_dual_kernel for K_s --
+    # and follow set_lattice_row_order() as apply() does.
+    @staticmethod
+    def _f32_only(t, name, what, f64_name):
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
+            raise TypeError(f"{what} takes float32 only, got {name} of torch.float64: the float64 form is {f64_name}")
+
+    def blur_t_f32(self, values, scratch=None, vd=None):
+        """The adjoint of the fp32 blur(): axes d .. 0, mirrored taps, the general kernel family (plx_blur_t).  Returns the
+        tensor that holds the result (either `values` or `scratch`), as blur() does."""
+        self._f32_only(values, "values", "blur_t_f32", "blur_t")
+        _check_f32_cuda(values, "values")
+        vd = values.shape[1] if vd is None else vd
+        assert values.shape[1] == self.values_stride(vd) and values.is_contiguous()
+        if values.shape[0] < self.m:
+            raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
+        if scratch is None:
+            scratch = torch.empty_like(values)
+        elif scratch.numel() < values.numel() or not scratch.is_contiguous() or scratch.dtype != values.dtype:
+            raise ValueError("scratch must be a contiguous float32 buffer, at least as large as values")
+        flag = ctypes.c_int(0)
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_blur_t(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), vd,
+                                     ctypes.byref(flag), _stream_ptr(self.device))
+        nv.check(rc, "plx_blur_t")
+        return scratch if flag.value else values
+
+    def blur_sym_f32(self, values, work=None, vd=None):
+        """0.5 * (blur(values) + blur_t_f32(values)) with the general family's bits, in d + 1 launches that advance both
+        chains (plx_blur_sym).  `values` [m, values_stride(vd)] float32 is clobbered; `work`: a contiguous float32 buffer
+        of at least plx_blur_sym_work_floats elements (allocated when None).  Returns an [m, stride] tensor that views
+        `values` or `work`, wherever the result lies."""
+        self._f32_only(values, "values", "blur_sym_f32", "blur_sym")
+        _check_f32_cuda(values, "values")
+        vd = values.shape[1] if vd is None else vd
+        stride = self.values_stride(vd)
+        assert values.shape[1] == stride and values.is_contiguous()
+        if values.shape[0] < self.m:
+            raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
+        need = int(nv.lib().plx_blur_sym_work_floats(self._h, vd))
+        if need < 0:
+            raise ValueError(f"blur_sym_f32 needs a built lattice and vd >= 1, got vd = {vd}")
+        if work is None:
+            work = torch.empty(need, dtype=torch.float32, device=self.device)
+        elif work.numel() < need or not work.is_contiguous() or work.dtype != torch.float32:
+            raise ValueError(f"work must be a contiguous float32 buffer of at least {need} elements")
+        res = ctypes.c_void_p(0)
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_blur_sym(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(work.data_ptr()), vd,
+                                       ctypes.byref(res), _stream_ptr(self.device))
+        nv.check(rc, "plx_blur_sym")
+        if res.value == values.data_ptr():
+            return values[:self.m]
+        off = (res.value - work.data_ptr()) // 4
+        return work.view(-1)[off:off + self.m * stride].view(self.m, stride)
+
+    def _apply_f32_variant(self, src, out, fn, what, f64_name):
+        self._f32_only(src, "src", what, f64_name)
+        self._f32_only(out, "out", what, f64_name)
+        _check_f32_cuda(src, "src")
+        src = self._src(src, self.n_owned)
+        vd = src.shape[1]
+        if out is None:
+            out = torch.empty((self.n_owned, vd), dtype=torch.float32, device=self.device)
+        else:
+            _check_f32_cuda(out, "out")
+        with torch.cuda.device(self.device):
+            rc = getattr(nv.lib(), fn)(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                                       _stream_ptr(self.device))
+        nv.check(rc, fn)
+        return out
+
+    def apply_t_f32(self, src, out=None):
+        """out = K^T src in float32: slice(blur_t_f32(splat(src))) on the workspace of apply() (plx_apply_t)."""
+        return self._apply_f32_variant(src, out, "plx_apply_t", "apply_t_f32", "apply_t")
+
+    def apply_sym_f32(self, src, out=None):
+        """out = K_s src in float32 with K_s = (K + K^T) / 2: slice(blur_sym_f32(splat(src))) (plx_apply_sym).  K_s is
+        symmetric to rounding; it is not proven positive."""
+        return self._apply_f32_variant(src, out, "plx_apply_sym", "apply_sym_f32", "apply_sym")
+
+    def apply_affine_sym_f32(self, src, scale_shift, out=None, want_dot=False):
+        """out = a * K_s src + b * src in float32 (plx_apply_affine_sym): apply_affine() with K_s for K -- the same
+        scale_shift, the same want_dot forms (True: (out, dots), 2..256 columns; "partial": (out, work, tiles) with the
+        per-tile partial sums left in the lattice's own buffer for the fused CG step)."""
+        self._f32_only(src, "src", "apply_affine_sym_f32", "apply_affine(symmetric=True)")
+        self._f32_only(scale_shift, "scale_shift", "apply_affine_sym_f32", "apply_affine(symmetric=True)")
+        _check_f32_cuda(src, "src")
+        src = self._src(src, self.n_owned)
+        _check_f32_cuda(scale_shift, "scale_shift", ndim=1)
+        assert scale_shift.numel() == 2 and scale_shift.is_contiguous()
+        vd = src.shape[1]
+        if out is None:
+            out = torch.empty((self.n_owned, vd), dtype=torch.float32, device=self.device)
+        else:
+            _check_f32_cuda(out, "out")
+        L = nv.lib()
+        dot = work = None
+        if want_dot:
+            need = int(L.plx_affine_dot_work_floats(self._h, vd))
+            if need < 0:
+                raise ValueError(f"apply_affine_sym_f32(want_dot=True) needs 2..256 columns on a built lattice, got {vd}")
+            if self._dot_work is None or self._dot_work.numel() < need:
+                self._dot_work = torch.empty(need, dtype=torch.float32, device=self.device)
+            work = self._dot_work
+            if want_dot != "partial":
+                dot = torch.empty(self.values_stride(vd), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = L.plx_apply_affine_sym(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                                        ctypes.c_void_p(scale_shift.data_ptr()),
+                                        ctypes.c_void_p(dot.data_ptr()) if dot is not None else None,
+                                        ctypes.c_void_p(work.data_ptr()) if work is not None else None,
+                                        _stream_ptr(self.device))
+        nv.check(rc, "plx_apply_affine_sym")
+        if want_dot == "partial":
+            return out, work, int(L.plx_affine_dot_tiles(self._h, vd))
+        return (out, dot[:vd]) if want_dot else out
+
+    def sym_kernels_f32(self):
+        """Kernels launched by the last transposed or symmetrised fp32 call: {"splat": [...], "blur": [...],
+        "slice": [...]}; stage_kernels() goes on naming the plain fp32 stages."""
+        return self._last_kernels("plx_last_sym_kernels", 512)
 
     # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
     def _rows(self, begin, count):

@@ -240,6 +240,10 @@ class LatticeFilterGeneral(Function):
     # The POSITION gradient is unchanged: it keeps the reference's symmetric treatment (py:113-122).  Off by default: the
     # reference's gradients are what every existing caller and test sees.
     exact_adjoint = False
+    # float32: the same switch for the default precision: grad_source = Lattice.apply_t_f32(g) (plx_apply_t) on the
+    # forward-tap lattice, in every branch of backward() that returns one, where `method` is None and the tensors are CUDA
+    # float32 2-D.  The position gradient is unchanged.  Off by default.
+    exact_adjoint_f32 = False
 
     @staticmethod
     def _filter():
@@ -267,7 +271,10 @@ class LatticeFilterGeneral(Function):
             d = ref.shape[-1]
             exact = (LatticeFilterGeneral.exact_adjoint and LatticeFilterGeneral.method is None and ctx.needs_input_grad[0]
                      and g.is_cuda and g.dim() == 2 and g.dtype == src.dtype == ref.dtype == torch.float64)
-            want_src = ctx.needs_input_grad[0] and not exact      # (exact: grad_source is formed once, at the end)
+            exact32 = (LatticeFilterGeneral.exact_adjoint_f32 and LatticeFilterGeneral.method is None
+                       and ctx.needs_input_grad[0] and g.is_cuda and g.dim() == 2
+                       and g.dtype == src.dtype == ref.dtype == torch.float32)
+            want_src = ctx.needs_input_grad[0] and not (exact or exact32)      # (exact: grad_source is formed once, at the end)
             if want_src and not ctx.needs_input_grad[1]:
                 # K is treated as symmetric (py:110-111)
                 grad_source = filt(g.contiguous(), ref.contiguous(), ctx.coeffs)
@@ -331,6 +338,10 @@ class LatticeFilterGeneral(Function):
                 # the adjoint of the forward product: K^T g with the forward taps (plx_apply_t_f64)
                 rc_ = ref if ref.is_contiguous() else carry_hint(ref.contiguous(), ref)
                 grad_source = _cache.get(rc_, ctx.coeffs).apply_t(g.contiguous())
+            elif exact32:
+                # ... and in float32 (plx_apply_t)
+                rc_ = ref if ref.is_contiguous() else carry_hint(ref.contiguous(), ref)
+                grad_source = _cache.get(rc_, ctx.coeffs).apply_t_f32(g.contiguous())
         return grad_source, grad_reference, None
 
 

@@ -1039,6 +1039,12 @@ class LatticeGP(nn.Module):
     # at small noise.  K_s is symmetric to rounding but NOT proven positive.  A pivoted-Cholesky preconditioner stays the
     # factor built from K: it is a preconditioner, not the operator.  Off by default: the solves see what they always saw.
     symmetric_f64 = False
+    # float32: the same switch for the default model.  True runs the fp32 branches of khat_solve (the native lattice-row-order
+    # iteration with its fused <P, AP> dot and its refinement, and the caller-order branch) and khat_in_lattice_rows on
+    # s K_s + sigma^2 I through Lattice.apply_affine_sym_f32 / apply_sym_f32.  The stall levels of plain CG on K lie orders
+    # above fp32 rounding, so the fp32 solves meet them as the double ones do.  The pivoted-Cholesky factor stays the one
+    # built from K.  Off by default.
+    symmetric_f32 = False
 
     def __init__(self, kernel, min_noise=1e-4):
         super().__init__()
@@ -1090,7 +1096,8 @@ class LatticeGP(nn.Module):
             ss = torch.stack([self.outputscale.detach().reshape(()), self.noise.detach().reshape(())]).to(torch.float32).contiguous()
             lat.set_lattice_row_order(True)
             try:
-                yield (lambda V: lat.apply_affine(V.contiguous(), ss)), lat.to_lattice_order, lat.from_lattice_order
+                affine = lat.apply_affine_sym_f32 if self.symmetric_f32 else lat.apply_affine
+                yield (lambda V: affine(V.contiguous(), ss)), lat.to_lattice_order, lat.from_lattice_order
             finally:
                 lat.set_lattice_row_order(False)
 
@@ -1183,7 +1190,10 @@ class LatticeGP(nn.Module):
                 if pre is not None and not (native_pre and rhs.shape[1] <= 16):
                     # a factor whose rows are in the caller's order: keep that order for the whole solve
                     lat.set_lattice_row_order(False)
-                    return batched_cg(lambda V: lat.apply(V).mul_(s).addcmul_(V, noise), rhs, **cg_args)
+                    product = lat.apply_sym_f32 if self.symmetric_f32 else lat.apply
+                    return batched_cg(lambda V: product(V).mul_(s).addcmul_(V, noise), rhs, **cg_args)
+                # symmetric_f32: K_s for K in every MVM of the iteration, its fused dots and the refinement
+                affine = lat.apply_affine_sym_f32 if self.symmetric_f32 else lat.apply_affine
                 ss = torch.stack([s.detach().reshape(()), noise.detach().reshape(())]).to(torch.float32).contiguous()
                 # columns padded to a multiple of 4 with zero right-hand sides: rows become whole 16-byte vectors, so
                 # splat reads the CG vectors in place (no padding copy) and slice writes 16 bytes per lane; a zero
@@ -1196,11 +1206,11 @@ class LatticeGP(nn.Module):
                 fused_dot = None
                 if 2 <= rhs_l.shape[1] <= 256:
                     def fused_dot(V):
-                        return lat.apply_affine(V, ss, want_dot=True)
-                    fused_dot.partial = lambda V: lat.apply_affine(V, ss, want_dot="partial")
-                sol, info = batched_cg(lambda V: lat.apply_affine(V, ss), rhs_l, matmul_dot=fused_dot, native_precond=native_pre,
+                        return affine(V, ss, want_dot=True)
+                    fused_dot.partial = lambda V: affine(V, ss, want_dot="partial")
+                sol, info = batched_cg(lambda V: affine(V, ss), rhs_l, matmul_dot=fused_dot, native_precond=native_pre,
                                        **cg_args)
-                sol, info = _refine_solution(lambda V: lat.apply_affine(V, ss), rhs_l, sol, info, fused_dot, native_pre, cg_args)
+                sol, info = _refine_solution(lambda V: affine(V, ss), rhs_l, sol, info, fused_dot, native_pre, cg_args)
                 if pad:
                     sol = sol[:, :t].contiguous()
                     info = dict(info, residual=info["residual"][:t])
