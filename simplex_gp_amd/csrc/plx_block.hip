@@ -23,6 +23,18 @@
 //           every point reads its d+1 (row, weight) pairs and the values from LDS.
 //
 // No MFMA: this is a gather / segmented-reduce path, bound by the corner stream (6 B per corner per side).
+//
+// Dependent loads (profiles/block_chains_measured.md; counted in the gfx950 assembly as full s_waitcnt vmcnt(0) between a
+// kernel's first load and its barrier).  A gather through an index is two round trips, and a rolled loop over such
+// gathers, or a branch around each of them, is two round trips PER ELEMENT: the compiler waits for every load in flight
+// before the dependent one.  So the staging loops are written as batches -- all indices, then all gathers, then the
+// stores -- with clamped addresses in place of predicates, so that no load sits behind a branch:
+//   slice_block_kernel    row values in batches of kSliceBatch passes of kBlkT rows: 2 waits per 2,048 rows (the rolled
+//                         loop: 2 per 256 rows, 12 at N = 1e6); then one round trip per kBlkT points;
+//   splat_combine_kernel  the four gathers of a lane together: 2 waits per step (a branch around each: 5);
+//   splat_block_kernel    its window loop waits for perm, then for src, once per kBlkT points (6 waits at 672 points).
+//                         Left as it is: with the window as one batch behind the corner records (1 wait) the kernel
+//                         took the same 20.5 us at N = 1e6 and 1 % more at N = 4e6 -- it is bound by its corner stream.
 
 #include "plx_kernels.h"
 
@@ -31,6 +43,7 @@ namespace plx {
 constexpr int kBlkT = 256;       // threads per block workgroup
 constexpr int kCombineRun = 256; // block rows per wave of splat_combine_kernel
 constexpr int kBlkMaxP = 1024;    // most points per block (d <= 2: fewer corners than a block could hold)
+constexpr int kSliceBatch = 8;    // passes of kBlkT block rows that slice_block_kernel stages as one batch of loads
 
 // exclusive scan of one int per thread over a kBlock-thread workgroup
 __device__ __forceinline__ int wg_exclusive_scan(int val, int *total)
@@ -239,14 +252,19 @@ __global__ __launch_bounds__(kBlock) void splat_combine_kernel(const int *__rest
             idx[4 * q] = ix.x; idx[4 * q + 1] = ix.y; idx[4 * q + 2] = ix.z; idx[4 * q + 3] = ix.w;
             vid[4 * q] = vx.x; vid[4 * q + 1] = vx.y; vid[4 * q + 2] = vx.z; vid[4 * q + 3] = vx.w;
         }
+        // the EPL gathers of a lane as one batch: an entry outside the wave's range reads partial[0] and is dropped by a
+        // select, not by a branch around its load (behind one, each gather waits for the one before: EPL round trips)
         float val[EPL];
         bool end[EPL];
 #pragma unroll
         for (int j = 0; j < EPL; ++j) {
             const bool live = k0 + j >= e0 && k0 + j < e1;
             end[j] = live && idx[j] < 0;
-            val[j] = live ? ((ablate & 1) ? 1.0f : partial[idx[j] & 0x7FFFFFFF]) : 0.f;
+            val[j] = (ablate & 1) ? 1.0f : partial[live ? idx[j] & 0x7FFFFFFF : 0];
         }
+#pragma unroll
+        for (int j = 0; j < EPL; ++j)
+            if (!(k0 + j >= e0 && k0 + j < e1)) val[j] = 0.f;
         // this thread's scan element (row ends seen, sum since the last row end): as in splat_block_kernel
         int icnt = 0;
         float itail = 0.f;
@@ -354,6 +372,26 @@ int splat_block_impl(plx_lattice *L, const float *d_src, float *d_values, hipStr
 // slice: one workgroup per block; out = sum_r w_r * values[v_r] / (1 + 2^-d) with the block's vertex values staged
 // in LDS.  Same arithmetic and order as slice_v1_kernel (plx_slice.hip).
 
+// NQ passes of kBlkT block rows from row j0 on: all ids of the batch, then -- one counted wait later -- all gathers
+// they address, then the LDS stores: two round trips per batch whatever NQ.  Threads past the last row take the last
+// row instead: they load its id and its value again and store that same value to its slot.  Nothing branches around a
+// load or a store, so the batch stays one straight run of code (behind a branch the compiler sinks a gather to its
+// store and waits for every load there, the next batch's included).
+template <int NQ>
+__device__ __forceinline__ void stage_row_values(const int *__restrict__ vid, const float *__restrict__ values, int j0, int rows,
+                                                 float *__restrict__ lds_val)
+{
+    const int tid = threadIdx.x;
+    int id[NQ];
+    float val[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) id[q] = vid[min(j0 + q * kBlkT + tid, rows - 1)];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) val[q] = values[id[q]];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) lds_val[min(j0 + q * kBlkT + tid, rows - 1)] = val[q];
+}
+
 template <int D1>
 __global__ __launch_bounds__(kBlkT) void slice_block_kernel(const uint16_t *__restrict__ srow, int64_t sstride,
                                                            const float *__restrict__ ew, int n,
@@ -372,7 +410,7 @@ __global__ __launch_bounds__(kBlkT) void slice_block_kernel(const uint16_t *__re
     // measured 10 % slower)
     uint32_t v[D1];
     float w[D1];
-    const int T = blockDim.x;
+    constexpr int T = kBlkT;
     int i = tid;
     if (i < np) {
 #pragma unroll
@@ -381,7 +419,11 @@ __global__ __launch_bounds__(kBlkT) void slice_block_kernel(const uint16_t *__re
             w[r] = ew[(size_t)r * n + own_begin + p0 + i];
         }
     }
-    for (int j = tid; j < rows; j += T) lds_val[j] = values[brow_vid[base + j]];
+    // row values, kSliceBatch passes of T rows per batch (a block has at least one row, so rows - 1 is a valid clamp).
+    // Every batch is the full size: a body picked by the number of passes left (a switch, or full / half) was tried, and
+    // the compiler chains such bodies behind each other and makes all but the first wait for every load in flight -- the
+    // first point's records -- before it issues its own ids, a round trip more than the few repeated loads cost.
+    for (int j0 = 0; j0 < rows; j0 += kSliceBatch * T) stage_row_values<kSliceBatch>(brow_vid + base, values, j0, rows, lds_val);
     __syncthreads();
     while (i < np) {
         float acc = 0.f;
