@@ -459,6 +459,31 @@ int plx_apply_affine_sym(plx_lattice *lat, const float *d_src, int vd, float *d_
 int plx_last_sym_kernels(const plx_lattice *lat, char *buf, int cap);
 
 /*
+ * The true diagonal of the operator (callers detect it by symbol; the version string is unchanged): K_ii of
+ * K = S B_d ... B_0 S^T / (1 + 2^-d), per point, exactly the sum the product forms -- not the unit diagonal the kernel
+ * classes declare.  With the corners v_a and the weights w_a of point i,
+ *     K_ii = (1 / (1 + 2^-d)) sum_{a,b} w_a w_b (B_d ... B_0)[v_a, v_b],
+ * and an entry of the blur product is a sum of at most 2 r + 1 paths through the neighbour table (one hop per axis, shifts
+ * c + s_j with s the 0 / +-1 pattern of the corner pair; csrc/plx_diag_kernels.h).  The taps are the lattice's own, those
+ * of its build.  diag(K^T) = diag(K), so the same values are the diagonal of plx_apply_t and of plx_apply_sym.
+ *   plx_diag      d_out[i - row_begin] = K_ii for the caller rows row_begin <= i < row_begin + row_count, every sum carried
+ *                 in fp32 (4-byte aligned).  On the stacked lattice [xout; xin] of a prediction the range of xin is
+ *                 diag K(x*, x*).  lattice_rows != 0: the same values in lattice position order (plx_copy_point_perm), for
+ *                 the whole range [0, n) only.  The call takes this flag and ignores plx_set_row_order.
+ *   plx_diag_f64  the same with every sum carried in double (the fp32 weights and taps converted exactly; 8-byte aligned).
+ * One launch, no workspace, no allocation, no synchronisation: legal under stream capture from the first call on;
+ * plx_device_bytes and what plx_last_kernels / plx_last_f64_kernels report are left as they were.  Refusals, all before the
+ * launch, the output untouched: a NULL pointer, row_count < 1, a range outside [0, n), lattice_rows with another range than
+ * [0, n), a misaligned output (PLX_ERR_INVALID); an unbuilt lattice, a sharded or merged one, a build that replayed
+ * "reference_growth" (its table is not symmetric and its splat weights differ from its slice weights) (PLX_ERR_STATE).
+ * Order 0 goes through the same code: c_0^(d+1) sum_a w_a^2 / (1 + 2^-d).  Every output element is written by one thread
+ * from sums in a fixed order, no atomics: two calls are bit-equal.  The fp32 values stay within
+ * ((d+1)^2 (2r+1) + d + 4) 2^-24 of the size of the terms they sum, the float64 ones within the same count of 2^-52.
+ */
+int plx_diag(plx_lattice *lat, int64_t row_begin, int64_t row_count, int lattice_rows, float *d_out, void *stream);
+int plx_diag_f64(plx_lattice *lat, int64_t row_begin, int64_t row_count, int lattice_rows, double *d_out, void *stream);
+
+/*
  * The float64 position gradient (callers detect it by symbol; the version string is unchanged): plx_apply_backward with
  * every array in double, for every column count.  `lat` is built with the DERIVATIVE taps on the positions rounded to
  * float, as for every fp64 call; d_x [n][d] is the caller's FLOAT64 position matrix (not the rounded copy), d_g (the

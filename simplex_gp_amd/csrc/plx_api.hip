@@ -956,6 +956,42 @@ int plx_last_sym_kernels(const plx_lattice *L, char *buf, int cap)
     return PLX_OK;
 }
 
+// ---- the true diagonal K_ii (kernel: plx_diag_kernels.h, instantiated by plx_diag.hip and plx_diag_f64.hip) ------------
+
+// Everything a diagonal call checks before its one launch.  `align`: bytes of an output element.
+static int check_diag(const plx_lattice *L, const void *d_out, int64_t begin, int64_t count, int lattice_rows, size_t align,
+                      const char *who)
+{
+    if (!L || !d_out) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
+    if (((uintptr_t)d_out & (align - 1)) != 0) {
+        set_error("%s: d_out must be %d-byte aligned", who, (int)align);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_range(L, begin, count, who));
+    if (lattice_rows && (begin != 0 || count != L->n)) {
+        set_error("%s: lattice_rows serves the whole range [0, %lld) only", who, (long long)L->n);
+        return PLX_ERR_INVALID;
+    }
+    return check_plain_build(L, "the diagonal is", who);
+}
+
+int plx_diag(plx_lattice *L, int64_t row_begin, int64_t row_count, int lattice_rows, float *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_diag(L, d_out, row_begin, row_count, lattice_rows, sizeof(float), "plx_diag"));
+    DeviceGuard g(L->device);
+    return diag_impl<float>(L, row_begin, row_count, lattice_rows != 0, d_out, (hipStream_t)stream);
+}
+
+int plx_diag_f64(plx_lattice *L, int64_t row_begin, int64_t row_count, int lattice_rows, double *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_diag(L, d_out, row_begin, row_count, lattice_rows, sizeof(double), "plx_diag_f64"));
+    DeviceGuard g(L->device);
+    return diag_impl<double>(L, row_begin, row_count, lattice_rows != 0, d_out, (hipStream_t)stream);
+}
+
 // ---- the float64 rectangular product (kernels: plx_rows_f64.hip; tables: plx_rows.hip; blur: plx_f64.hip) --------------
 
 // check_rows and check_f64 in one: the checks of both, each once.

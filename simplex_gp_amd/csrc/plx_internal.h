@@ -493,6 +493,12 @@ template <typename T>
 int backward_contract_rows_impl(plx_lattice *L, const T *d_values, const T *d_b, int64_t b_begin, int64_t b_count, const T *d_x,
                                 int nrhs, T *d_grad_x, T *d_filtered, hipStream_t stream);
 
+// plx_diag_kernels.h, instantiated by plx_diag.hip (float) and plx_diag_f64.hip (double): d_out[i - row_begin] = K_ii for
+// the caller rows of the range, or with lattice_rows d_out[p] for every lattice position p (arguments checked by the entry
+// points).  One launch; no table built, no workspace, no kernel name recorded.
+template <typename T>
+int diag_impl(plx_lattice *L, int64_t row_begin, int64_t row_count, bool lattice_rows, T *d_out, hipStream_t stream);
+
 // contiguous near-equal row blocks: the first n % shards blocks get one extra row
 inline void shard_range(int64_t n, int shards, int index, int64_t *lo, int64_t *hi)
 {

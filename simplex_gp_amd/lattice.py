@@ -622,6 +622,32 @@ class Lattice:
         "slice": [...]}; stage_kernels() goes on naming the plain fp32 stages."""
         return self._last_kernels("plx_last_sym_kernels", 512)
 
+    # -- the true diagonal (plx_diag / plx_diag_f64) ---------------------------
+    def diag(self, dtype=torch.float32, rows=None, lattice_rows=False, out=None):
+        """K_ii of K = S B_d ... B_0 S^T / (1 + 2^-d) with this build's taps, per point -- what the product computes, not
+        the unit diagonal the kernel classes declare; also the diagonal of K^T and of K_s.  Every sum is carried in `dtype`
+        (torch.float32: plx_diag, torch.float64: plx_diag_f64).  rows = (begin, count): the caller rows of that range only
+        (on a stacked lattice [xout; xin] the range of xin is diag K(x*, x*)).  lattice_rows: the values in lattice position
+        order, the whole range only; the call ignores set_lattice_row_order.  One launch, no workspace: graph-capturable."""
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"diag: dtype is torch.float32 or torch.float64, got {dtype}")
+        fn = "plx_diag" if dtype == torch.float32 else "plx_diag_f64"
+        if not nv.has_symbols(fn):
+            raise RuntimeError(f"diag: this libplx.so does not export {fn}: rebuild it (make -C simplex_gp_amd/csrc)")
+        begin, count = (0, self.n) if rows is None else self._rows(*rows)
+        if lattice_rows and (begin, count) != (0, self.n):
+            raise ValueError(f"diag(lattice_rows=True) serves the whole range [0, {self.n}) only")
+        if out is None:
+            out = torch.empty(count, dtype=dtype, device=self.device)
+        else:
+            assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and out.numel() == count, \
+                f"out must be a contiguous {dtype} CUDA tensor of {count} elements"
+        with torch.cuda.device(self.device):
+            rc = getattr(nv.lib(), fn)(self._h, begin, count, 1 if lattice_rows else 0, ctypes.c_void_p(out.data_ptr()),
+                                       _stream_ptr(self.device))
+        nv.check(rc, fn)
+        return out
+
     # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
     def _rows(self, begin, count):
         begin, count = int(begin), int(count)

@@ -428,7 +428,11 @@ def _lattice_matvec(rhs, positions, dkernel):
 
 class SquareLazyLattice(LazyTensor):
     """K(x, x), known through its action only (py:127-140): symmetric by declaration (its transpose is itself,
-    py:137-138) and with a unit diagonal by declaration (py:139-140), whatever the lattice actually computes."""
+    py:137-138) and with a unit diagonal by declaration (py:139-140), whatever the lattice actually computes.  The
+    declared diagonal has a true counterpart, the K_ii the product forms (Lattice.diag, plx_diag / plx_diag_f64): with the
+    class switch `true_diag` on, diag() of a CUDA operator on a plain build returns it."""
+
+    true_diag = False      # class switch: diag() returns the operator's own diagonal where the native call serves it
 
     def __init__(self, x, dkernel=None, symmetrized=False):
         super().__init__(x, dkernel=dkernel, symmetrized=symmetrized)
@@ -454,7 +458,14 @@ class SquareLazyLattice(LazyTensor):
         return self
 
     def diag(self):
-        return self.x.new_ones(self.x.shape[:-1])
+        x = self.x
+        if self.true_diag and x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.float64):
+            xc = x.detach()
+            xc = xc if xc.is_contiguous() else carry_hint(xc.contiguous(), xc)
+            lat = _cache.get(xc, self.dkernel.get_coeffs())      # the forward-tap lattice of the products
+            if lat.accepts_rows():
+                return lat.diag(dtype=x.dtype)
+        return x.new_ones(x.shape[:-1])
 
 
 class RectangularLazyLattice(LazyTensor):
@@ -561,7 +572,8 @@ class RectangularLazyLattice(LazyTensor):
 class LatticeAccelerated(Kernel):
     """A stationary kernel, given as a differentiable profile in the squared distance, evaluated through the
     permutohedral lattice (py:183-200).  ARD lengthscales divide the inputs before they reach the lattice (py:198-200);
-    the diagonal is reported as ones (py:193-195)."""
+    the diagonal is reported as ones (py:193-195); the diagonal the lattice computes is Lattice.diag (and
+    SquareLazyLattice.diag() under its `true_diag` switch)."""
 
     has_lengthscale = True
 

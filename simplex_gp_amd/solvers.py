@@ -132,7 +132,7 @@ class PivotedCholeskyPreconditioner:
     preconditioner GPyTorch builds for (s K + sigma^2 I) when max_preconditioner_size > 0
     (experiments/train_simplexgp.py:34-41 runs with pre_size = 100, configs/simplexgp.yml).
 
-    The factor needs the diagonal of K (ones: py:139-140) and k rows of it; a row is one
+    The factor needs the diagonal of K (ones: py:139-140; `true_diag`: the [n] diagonal the operator computes) and k rows of it; a row is one
     MVM with a one-hot right-hand side (the operator is known through matmul only).  The
     pivot index stays on the device (scatter with an index tensor), so the k steps queue
     without host synchronisation.
@@ -142,11 +142,16 @@ class PivotedCholeskyPreconditioner:
     sample(t) = t columns drawn from N(0, P):  L g1 + sigma g2
     """
 
-    def __init__(self, kmatmul, n, outputscale, noise, rank, device, dtype=torch.float32, rel_tol=1e-6):
+    def __init__(self, kmatmul, n, outputscale, noise, rank, device, dtype=torch.float32, rel_tol=1e-6, true_diag=False):
         s, noise = float(outputscale), float(noise)
         rank = int(min(rank, n))
         Lt = torch.zeros(rank, n, dtype=dtype, device=device)           # L^T: every pivot's column is one contiguous row
-        diag = torch.full((n,), s, dtype=dtype, device=device)          # s * diag(K), diag(K) = 1
+        if true_diag is None or true_diag is False:
+            diag = torch.full((n,), s, dtype=dtype, device=device)      # s * diag(K), diag(K) = 1 by declaration
+        else:
+            # true_diag: the operator's own diagonal, [n] in the caller's row order (Lattice.diag) -- the residual diagonal
+            # then starts at what the rows K e_p actually hold at their pivots
+            diag = s * torch.as_tensor(true_diag, dtype=dtype, device=device).reshape(n)
         onehot = torch.zeros(n, 1, dtype=dtype, device=device)
         for m in range(rank):
             piv = torch.argmax(diag).reshape(1)
@@ -281,6 +286,8 @@ class LatticePreconditioner:
         the updated residual diagonal: exact_steps, None = when it pays) -- the factor is the sequential algorithm's,
         pivot for pivot (ties broken by the caller's row number, like torch.argmax on the caller-order diagonal), at
         one host read-back per batch;
+      * true_diag=True starts the residual diagonal at s K_ii, the diagonal the lattice computes (Lattice.diag), instead
+        of the declared s * 1; off by default;
       * solve() = plx_pcg_project (L^T R on the matrix cores, C^-1 in fp64) + plx_pcg_apply;
       * the finished factor is kept in fp16 (factor_dtype; fp32 on request): both passes of an application stream the
         factor and nothing else of size, so its width is their time.  The factor is BUILT in fp32 and rounded once;
@@ -293,7 +300,7 @@ class LatticePreconditioner:
     SPARSE_ROWS_MAX_FRACTION = 0.5    # kernel rows are computed on the frontier of their non-zero vertex rows while a batch's frontier stays under this share of the lattice
 
     def __init__(self, lat, outputscale, noise, rank, rel_tol=1e-6, batch=16, factor_dtype=torch.float16, sparse_rows=True,
-                 exact_steps=None):
+                 exact_steps=None, true_diag=False):
         import ctypes
         from . import _native as nv
         lib = nv.lib()
@@ -317,7 +324,12 @@ class LatticePreconditioner:
             self.Lt[k:].zero_()
         if ld > n:
             self.Lt[:, n:].zero_()
-        diag = torch.full((n,), s, dtype=torch.float32, device=dev)
+        if true_diag:
+            # the residual diagonal starts at s K_ii, the diagonal the lattice computes (plx_diag), in the order the factor
+            # keeps it: lattice position order, row_rank[i] naming the caller row of position i
+            diag = lat.diag(dtype=torch.float32, lattice_rows=True).mul_(s)
+        else:
+            diag = torch.full((n,), s, dtype=torch.float32, device=dev)      # diag(K) = 1 by declaration
         row_rank = torch.empty(lat.n, dtype=torch.int32, device=dev)          # caller row of every lattice position (uint32 bits)
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -527,11 +539,12 @@ class LatticePreconditioner64(LatticePreconditioner):
       * solve() = plx_pcg_project_f64 + plx_pcg_apply_f64 on double vectors; a float32 R is a TypeError.
     """
 
-    def __init__(self, lat, outputscale, noise, rank, rel_tol=1e-6, batch=16, sparse_rows=True, exact_steps=None):
+    def __init__(self, lat, outputscale, noise, rank, rel_tol=1e-6, batch=16, sparse_rows=True, exact_steps=None,
+                 true_diag=False):
         from . import _native as nv
         lib = nv.lib()
         super().__init__(lat, outputscale, noise, rank, rel_tol=rel_tol, batch=batch, factor_dtype=torch.float32,
-                         sparse_rows=sparse_rows, exact_steps=exact_steps)
+                         sparse_rows=sparse_rows, exact_steps=exact_steps, true_diag=true_diag)
         dev, n, k, kp, ld, noise = lat.device, self.n, self.rank, self.kp, self.ld, self.noise
         rows = torch.zeros(kp, ld, dtype=torch.float32, device=dev)
         rows[:, :n].index_copy_(1, lat.shard_perm(), self.Lt[:, :n])      # column perm[i] (caller row) <- lattice row i
