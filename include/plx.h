@@ -484,6 +484,43 @@ int plx_diag(plx_lattice *lat, int64_t row_begin, int64_t row_count, int lattice
 int plx_diag_f64(plx_lattice *lat, int64_t row_begin, int64_t row_count, int lattice_rows, double *d_out, void *stream);
 
 /*
+ * Queries at points that are not the build's (callers detect them by symbol; the version string is unchanged): locate
+ * foreign points in a built lattice once, then slice any vertex array there, without a new build.  The operator is
+ *     K_q(x*, X) = S* B_d ... B_0 S_X^T / (1 + 2^-d),
+ * where S* holds a query's barycentric weights on those of its d + 1 simplex corners that are vertices of X's lattice; an
+ * absent corner contributes nothing.  It is NOT the stacked operator of plx_apply_rows on [x*; X], whose blur also runs
+ * through vertices that exist only because of the query points; how much of a query the lattice supports is data-dependent,
+ * which is why plx_locate reports the weight mass it found.
+ *   plx_locate    d_x [nq][d] in the units of plx_build's d_ref (already divided by the lengthscale).  d_vid [d+1][nq] int32
+ *                 and d_w [d+1][nq] float have the SoA layout of the build's corner tables: d_vid[r][q] is the id of corner r
+ *                 in the numbering of the CURRENT build, or -1 when that key is not a vertex; d_w[r][q] is always the
+ *                 barycentric weight, with the bits the build gives a point at the same position.  d_mass (may be NULL)
+ *                 [nq]: the fp32 sum, in corner order, of the weights of the corners found -- 1 where the whole simplex
+ *                 exists.  A query with a coordinate outside the int16 key range, NaN or Inf gets every id -1 and mass 0;
+ *                 that is no error and the lattice stays usable.  A location is stale after the next build of `lat`; the
+ *                 library cannot know (simplex_gp_amd.lattice.LatticeQuery carries the build id).
+ *   plx_slice_at / plx_slice_at_f64
+ *                 d_values: a vertex array with row stride plx_values_stride(vd) / plx_values_stride_f64(vd), as plx_splat +
+ *                 plx_blur (or their _f64 forms) leave it, in whichever buffer the blur reports; 16-byte aligned for
+ *                 vd > 1.  d_out [nq][vd], dense, in query order:
+ *                     out[q][c] = sum over r with vid >= 0 of w_r values[vid_r][c] / (1 + 2^-d),
+ *                 in the expression forms and corner order of plx_slice_rows / plx_slice_f64: for a query at a build point
+ *                 the bits of that point's row of those calls.  An absent corner is skipped, not multiplied by zero.
+ *   plx_last_query_kernels  "locate=...;slice_at=..." of the last such calls.
+ * Each call is one launch: no workspace, no allocation, no read-back, legal under stream capture.  Refusals, all before
+ * the launch, the outputs untouched: a NULL pointer (d_mass excepted), nq < 1, vd < 1, a misaligned buffer, an output
+ * that aliases an input (PLX_ERR_INVALID); an unbuilt lattice, a sharded or merged one, a build that replayed
+ * "reference_growth", the single-use lattice of plx_filter (PLX_ERR_STATE); m * stride or nq * stride >= 2^31
+ * (PLX_ERR_TOO_LARGE), the column limit of plx_slice_rows / plx_slice_f64.
+ */
+int plx_locate(plx_lattice *lat, const float *d_x, int64_t nq, int32_t *d_vid, float *d_w, float *d_mass, void *stream);
+int plx_slice_at(plx_lattice *lat, const float *d_values, int vd, const int32_t *d_vid, const float *d_w, int64_t nq,
+                 float *d_out, void *stream);
+int plx_slice_at_f64(plx_lattice *lat, const double *d_values, int vd, const int32_t *d_vid, const float *d_w, int64_t nq,
+                     double *d_out, void *stream);
+int plx_last_query_kernels(const plx_lattice *lat, char *buf, int cap);
+
+/*
  * The float64 position gradient (callers detect it by symbol; the version string is unchanged): plx_apply_backward with
  * every array in double, for every column count.  `lat` is built with the DERIVATIVE taps on the positions rounded to
  * float, as for every fp64 call; d_x [n][d] is the caller's FLOAT64 position matrix (not the rounded copy), d_g (the

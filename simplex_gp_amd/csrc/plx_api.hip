@@ -992,6 +992,99 @@ int plx_diag_f64(plx_lattice *L, int64_t row_begin, int64_t row_count, int latti
     return diag_impl<double>(L, row_begin, row_count, lattice_rows != 0, d_out, (hipStream_t)stream);
 }
 
+// ---- queries at foreign points (locate_kernel: plx_build.hip; the slices: plx_query_kernels.h) --------------------------
+
+// What every query call checks about the lattice: built, plain, and not the single-use lattice of plx_filter.
+static int check_query_lattice(const plx_lattice *L, const char *who)
+{
+    if (!L->built) { set_error("%s: lattice not built", who); return PLX_ERR_STATE; }
+    PLX_TRY(check_plain_build(L, "queries are", who));
+    if (L->single_use) {
+        set_error("%s: this lattice was built by plx_filter for one product; queries are served by plx_build lattices", who);
+        return PLX_ERR_STATE;
+    }
+    return PLX_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+int plx_locate(plx_lattice *L, const float *d_x, int64_t nq, int32_t *d_vid, float *d_w, float *d_mass, void *stream)
+{
+    const char *who = "plx_locate";
+    EntryScope sc(L, stream);
+    if (!L || !d_x || !d_vid || !d_w) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (nq < 1) { set_error("%s: nq = %lld must be positive", who, (long long)nq); return PLX_ERR_INVALID; }
+    if ((((uintptr_t)d_x | (uintptr_t)d_vid | (uintptr_t)d_w | (uintptr_t)d_mass) & 3) != 0) {
+        set_error("%s: buffers must be 4-byte aligned", who);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_query_lattice(L, who));
+    const int d1 = L->d + 1;
+    if (nq * d1 >= (1ll << 31)) { set_error("%s: nq*(d+1) exceeds 2^31 elements; split the queries", who); return PLX_ERR_TOO_LARGE; }
+    const size_t nx = (size_t)nq * L->d * 4, ne = (size_t)nq * d1 * 4, nm = (size_t)nq * 4;
+    if (ranges_overlap(d_x, nx, d_vid, ne) || ranges_overlap(d_x, nx, d_w, ne) || ranges_overlap(d_vid, ne, d_w, ne) ||
+        (d_mass && (ranges_overlap(d_x, nx, d_mass, nm) || ranges_overlap(d_vid, ne, d_mass, nm) ||
+                    ranges_overlap(d_w, ne, d_mass, nm)))) {
+        set_error("%s: the outputs must not overlap the queries or each other", who);
+        return PLX_ERR_INVALID;
+    }
+    DeviceGuard g(L->device);
+    return locate_impl(L, d_x, nq, d_vid, d_w, d_mass, (hipStream_t)stream);
+}
+
+// Everything a slice_at call checks before its one launch.  `esz`: bytes of a value; `stride`: elements of a vertex row.
+static int check_slice_at(const plx_lattice *L, const void *d_values, int vd, const void *d_vid, const void *d_w, int64_t nq,
+                          const void *d_out, size_t esz, int stride, const char *who)
+{
+    if (!L || !d_values || !d_vid || !d_w || !d_out) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (nq < 1) { set_error("%s: nq = %lld must be positive", who, (long long)nq); return PLX_ERR_INVALID; }
+    if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    if ((((uintptr_t)d_vid | (uintptr_t)d_w) & 3) != 0 || (((uintptr_t)d_values | (uintptr_t)d_out) & (esz - 1)) != 0) {
+        set_error("%s: buffers must be aligned to their element size", who);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, who));
+    PLX_TRY(check_query_lattice(L, who));
+    PLX_TRY(check_size(L, stride, nq, "nq", who));
+    const size_t no = (size_t)nq * vd * esz, ne = (size_t)nq * (L->d + 1) * 4, nv = (size_t)L->m * stride * esz;
+    if (ranges_overlap(d_out, no, d_values, nv) || ranges_overlap(d_out, no, d_vid, ne) || ranges_overlap(d_out, no, d_w, ne)) {
+        set_error("%s: d_out must not overlap d_values, d_vid or d_w", who);
+        return PLX_ERR_INVALID;
+    }
+    return PLX_OK;
+}
+
+int plx_slice_at(plx_lattice *L, const float *d_values, int vd, const int32_t *d_vid, const float *d_w, int64_t nq, float *d_out,
+                 void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_slice_at(L, d_values, vd, d_vid, d_w, nq, d_out, sizeof(float), vd >= 1 ? values_stride(vd) : 1, "plx_slice_at"));
+    DeviceGuard g(L->device);
+    return slice_at_impl<float>(L, d_values, vd, d_vid, d_w, nq, d_out, (hipStream_t)stream);
+}
+
+int plx_slice_at_f64(plx_lattice *L, const double *d_values, int vd, const int32_t *d_vid, const float *d_w, int64_t nq,
+                     double *d_out, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_slice_at(L, d_values, vd, d_vid, d_w, nq, d_out, sizeof(double), vd >= 1 ? values_stride_f64(vd) : 1,
+                           "plx_slice_at_f64"));
+    DeviceGuard g(L->device);
+    return slice_at_impl<double>(L, d_values, vd, d_vid, d_w, nq, d_out, (hipStream_t)stream);
+}
+
+int plx_last_query_kernels(const plx_lattice *L, char *buf, int cap)
+{
+    if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
+    snprintf(buf, (size_t)cap, "locate=%s;slice_at=%s", L->kn_locate, L->kn_slice_at);
+    return PLX_OK;
+}
+
 // ---- the float64 rectangular product (kernels: plx_rows_f64.hip; tables: plx_rows.hip; blur: plx_f64.hip) --------------
 
 // check_rows and check_f64 in one: the checks of both, each once.

@@ -494,6 +494,30 @@ __device__ __forceinline__ void rec_key(const int (&gr)[D], const int (&rk)[D + 
 // ----------------------------------------------------------------------------
 // embed: h:395-471 for one point per thread, everything in registers
 
+// h:460-465.  rank is a permutation of 0..d, so every barycentric cell gets
+// exactly one "+=" and one "-=": bary[k] = delta[rank == d-k] - delta[rank == d+1-k].
+// Select instead of indexing by rank (a runtime index would spill to scratch).
+// Shared by the embedding and by locate_kernel, so a query at a build point's position gets that point's weights, bit for bit.
+template <int D>
+__device__ __forceinline__ void barycentric(const float (&el)[D + 1], const int (&gr)[D + 1], const int (&rk)[D + 1],
+                                            float (&bary)[D + 1])
+{
+    constexpr int D1 = D + 1;
+    constexpr float scale = 1.0f / (float)D1;
+    float sd[D1];   // delta ordered by rank
+#pragma unroll
+    for (int k = 0; k < D1; ++k) sd[k] = 0.f;
+#pragma unroll
+    for (int i = 0; i < D1; ++i) {
+        float delta = (el[i] - (float)gr[i]) * scale;
+#pragma unroll
+        for (int k = 0; k < D1; ++k) sd[k] = (rk[i] == k) ? delta : sd[k];
+    }
+#pragma unroll
+    for (int k = 1; k <= D; ++k) bary[k] = sd[D - k] - sd[D1 - k];
+    bary[0] = sd[D] + (1.0f + (0.0f - sd[0]));
+}
+
 template <int D>
 __global__ __launch_bounds__(kBlock) void embed_kernel(const float *__restrict__ x,
                                                        const uint32_t *__restrict__ perm, int n, ScaleArgs sf,
@@ -513,26 +537,11 @@ __global__ __launch_bounds__(kBlock) void embed_kernel(const float *__restrict__
     elevate<D>(pos, sf, el);
 
     // h:405-457
-    constexpr float scale = 1.0f / (float)D1;
     int gr[D1], rk[D1];
     const bool bad = nearest_vertex<D>(el, gr, rk);
 
-    // h:460-465.  rank is a permutation of 0..d, so every barycentric cell gets
-    // exactly one "+=" and one "-=": bary[k] = delta[rank == d-k] - delta[rank == d+1-k].
-    // Select instead of indexing by rank (a runtime index would spill to scratch).
-    float sd[D1];   // delta ordered by rank
-#pragma unroll
-    for (int k = 0; k < D1; ++k) sd[k] = 0.f;
-#pragma unroll
-    for (int i = 0; i < D1; ++i) {
-        float delta = (el[i] - (float)gr[i]) * scale;
-#pragma unroll
-        for (int k = 0; k < D1; ++k) sd[k] = (rk[i] == k) ? delta : sd[k];
-    }
     float bary[D1];
-#pragma unroll
-    for (int k = 1; k <= D; ++k) bary[k] = sd[D - k] - sd[D1 - k];
-    bary[0] = sd[D] + (1.0f + (0.0f - sd[0]));
+    barycentric<D>(el, gr, rk, bary);
 
     if (bad) atomicOr(&counters[1], 1);
 
@@ -1798,6 +1807,19 @@ static int table_fp_on(plx_lattice *L, int64_t m)
     return on;
 }
 
+// scale factors exactly as the reference computes them (h:372-390); the build's and, from the same taps, plx_locate's
+template <int D>
+static ScaleArgs scale_args(const plx_lattice *L)
+{
+    ScaleArgs sf;
+    for (int i = 0; i < D; ++i) {
+        sf.v[i] = 1.0f / (sqrtf((float)(i + 1) * (i + 2)));
+        float sigma_blur = taps_variance(L->taps.c, L->ntaps);
+        sf.v[i] *= (D + 1) * sqrtf(sigma_blur + 1.0f / 6.0f);
+    }
+    return sf;
+}
+
 // ---- stage 1: everything that depends only on this lattice's own points --------------------
 // order, embed, hashed insert, first-touch numbering, per-corner vertex ids.  Leaves L->m (the
 // number of vertices THESE points touch), vkeys, evid, ew, perm and the key -> id table.
@@ -1811,13 +1833,7 @@ static int stage_local(plx_lattice *L, const float *d_ref, hipStream_t stream, i
     const int nblocks = ceil_div(n, kBlock);
     auto mark = [&]() { if (L->timing) (void)hipEventRecord(L->ev[(*evi)++], stream); };
 
-    // scale factors exactly as the reference computes them (h:372-390)
-    ScaleArgs sf;
-    for (int i = 0; i < D; ++i) {
-        sf.v[i] = 1.0f / (sqrtf((float)(i + 1) * (i + 2)));
-        float sigma_blur = taps_variance(L->taps.c, L->ntaps);
-        sf.v[i] *= (D + 1) * sqrtf(sigma_blur + 1.0f / 6.0f);
-    }
+    const ScaleArgs sf = scale_args<D>(L);
     L->slice_denom = 1 + powf(2, -D);
 
     // table capacity: power of two >= 2E  (load factor <= 0.5)
@@ -2285,6 +2301,111 @@ static int merge_typed(plx_lattice *L, const uint32_t *d_all_keys, const int64_t
     return rc;
 }
 
+// ----------------------------------------------------------------------------
+// locate (plx_locate): the embedding of a point that is NOT one of the build's, looked up in the build's key -> id table.
+// One query per thread, everything in registers: elevate / nearest_vertex / barycentric are the embedding's own code (so a
+// query at a build point's position gets that point's simplex and weights, bit for bit), rec_key gives the corner keys, and
+// the lookup is the probe loop of neighbor_kernel.  The d + 1 probes of a query are independent chains of dependent gathers
+// (table word, then key).  They run in groups of locate_chains(d) corners, as the insert runs its corners (a group's keys
+// stay in registers: the whole simplex would be 528 registers at d = 32, and the unrolled code of it compiles for minutes):
+// every round issues the table loads of all pending corners of the group before any key load, and where the table words
+// carry a fingerprint a key is only fetched when the byte matches.
+// vid / w: SoA [d + 1][nq] as evid / ew; vid = -1 where the corner's key is not a vertex of this lattice.  mass: the fp32
+// sum, in corner order, of the weights of the corners found.  A query out of the key range (or NaN / Inf) finds nothing; the
+// build's error flag is not touched.  The occupancy bitmap of large builds (slotmap) is not consulted: it spares a table
+// read only where the slot is empty, and the queries this serves mostly find their corners.
+constexpr int locate_chains(int d) { return d <= 3 ? d + 1 : (d <= 10 ? 3 : (d <= 20 ? 2 : 1)); }
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void locate_kernel(const float *__restrict__ x, int64_t nq, ScaleArgs sf,
+                                                        const uint32_t *__restrict__ table, HashSel hs, uint32_t idmask,
+                                                        int fp_on, const uint32_t *__restrict__ vkeys,
+                                                        int *__restrict__ vid, float *__restrict__ w, float *__restrict__ mass)
+{
+    constexpr int D1 = D + 1;
+    constexpr int DW = (D + 1) / 2;
+    constexpr int G = locate_chains(D);
+    static_assert(D1 <= 64, "one bit per corner in the found mask");
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= nq) return;
+    float pos[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) pos[i] = x[(size_t)q * D + i];
+    float el[D1];
+    elevate<D>(pos, sf, el);
+    int gr[D1], rk[D1];
+    const bool bad = nearest_vertex<D>(el, gr, rk);
+    float bary[D1];
+    barycentric<D>(el, gr, rk, bary);
+    int g0[D];      // what the point records keep: the first d coordinates
+#pragma unroll
+    for (int i = 0; i < D; ++i) g0[i] = gr[i];
+
+    unsigned long long foundmask = 0;
+    for (int r0 = 0; r0 < D1; r0 += G) {
+        uint32_t k[G][DW], h[G], fp[G], o[G];
+        int found[G];
+        bool pend[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int r = r0 + g;
+            rec_key<D>(g0, rk, r < D1 ? r : 0, k[g]);
+            h[g] = hash_slot(key_hash<D>(k[g], hs), hs);
+            fp[g] = lin_fp(lin_hash_packed<D>(k[g]));
+            o[g] = kEmpty;
+            found[g] = -1;
+            pend[g] = !bad && r < D1;
+        }
+        bool any = true;
+        while (any) {
+            any = false;
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (pend[g]) o[g] = table[h[g]];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (!pend[g]) continue;
+                if (o[g] == kEmpty) { pend[g] = false; continue; }
+                if (!fp_on || (o[g] >> kFpShift) == fp[g]) {
+                    const uint32_t v = o[g] & idmask;
+                    uint32_t kv[DW];
+                    load_key<DW>(vkeys, (size_t)v, kv);
+                    if (key_equal<DW>(k[g], kv)) { found[g] = (int)v; pend[g] = false; continue; }
+                }
+                h[g] = (h[g] + 1) & hs.mask;
+                any = true;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int r = r0 + g;
+            if (r < D1) {
+                vid[(size_t)r * nq + q] = found[g];
+                if (found[g] >= 0) foundmask |= 1ull << r;
+            }
+        }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int r = 0; r < D1; ++r) {
+        w[(size_t)r * nq + q] = bary[r];
+        if ((foundmask >> r) & 1ull) sum += bary[r];
+    }
+    if (mass) mass[q] = sum;
+}
+
+template <int D>
+static int locate_typed(plx_lattice *L, const float *d_x, int64_t nq, int32_t *d_vid, float *d_w, float *d_mass,
+                        hipStream_t stream)
+{
+    locate_kernel<D><<<ceil_div(nq, kBlock), kBlock, 0, stream>>>(d_x, nq, scale_args<D>(L), L->table.as<uint32_t>(), hash_sel(L),
+                                                                  L->table_idmask, L->table_idmask != 0xFFFFFFFFu ? 1 : 0,
+                                                                  L->vkeys.as<uint32_t>(), d_vid, d_w, d_mass);
+    PLX_HIP_TRY(hipGetLastError());
+    L->kn_locate = "locate_kernel";
+    return PLX_OK;
+}
+
 #define PLX_DIM_SWITCH(CALL)                                                                                  \
     switch (L->d) {                                                                                           \
         PLX_CASE(1) PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8)       \
@@ -2299,6 +2420,13 @@ static int merge_typed(plx_lattice *L, const uint32_t *d_all_keys, const int64_t
 int build_impl(plx_lattice *L, const float *d_ref, hipStream_t stream)
 {
 #define PLX_CASE(D) case D: return build_typed<D>(L, d_ref, stream);
+    PLX_DIM_SWITCH()
+#undef PLX_CASE
+}
+
+int locate_impl(plx_lattice *L, const float *d_x, int64_t nq, int32_t *d_vid, float *d_w, float *d_mass, hipStream_t stream)
+{
+#define PLX_CASE(D) case D: return locate_typed<D>(L, d_x, nq, d_vid, d_w, d_mass, stream);
     PLX_DIM_SWITCH()
 #undef PLX_CASE
 }

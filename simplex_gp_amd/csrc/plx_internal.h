@@ -314,6 +314,9 @@ struct plx_lattice {
     // first such call of a width, and the kernels of the last transposed or symmetrised fp32 call
     plx::DevBuf val_s;                        // float [2][m][plx_values_stride(vd)]
     const char *kn_sym32_splat = "", *kn_sym32_blur = "", *kn_sym32_slice = "";   // plx_last_sym_kernels
+
+    // queries at points that are not the build's (plx_locate in plx_build.hip, plx_slice_at in plx_query_kernels.h)
+    const char *kn_locate = "", *kn_slice_at = "";   // kernels of the last query calls (plx_last_query_kernels)
 };
 
 namespace plx {
@@ -326,6 +329,8 @@ int refuse_under_capture(hipStream_t stream, const char *what);
 // plx_build.hip
 int build_impl(plx_lattice *L, const float *d_ref, hipStream_t stream);
 int build_local_impl(plx_lattice *L, const float *d_ref, hipStream_t stream);
+// plx_locate: the corners of nq foreign points in the current build's numbering (arguments checked by the entry point)
+int locate_impl(plx_lattice *L, const float *d_x, int64_t nq, int32_t *d_vid, float *d_w, float *d_mass, hipStream_t stream);
 int build_merge_impl(plx_lattice *L, const uint32_t *d_all_keys, const int64_t *h_counts, int n_ranks, int my_rank,
                      hipStream_t stream);
 int read_back(plx_lattice *L, const int *d_src, int count, int *h_dst, hipStream_t stream);   // a few device ints to the host, no stream synchronisation
@@ -498,6 +503,13 @@ int backward_contract_rows_impl(plx_lattice *L, const T *d_values, const T *d_b,
 // points).  One launch; no table built, no workspace, no kernel name recorded.
 template <typename T>
 int diag_impl(plx_lattice *L, int64_t row_begin, int64_t row_count, bool lattice_rows, T *d_out, hipStream_t stream);
+
+// plx_query_kernels.h, instantiated by plx_query.hip (float) and plx_query_f64.hip (double): d_out[q][c] = the slice of the
+// vertex array at the located corners of query q, absent corners (id -1) skipped (arguments checked by the entry points).
+// One launch; no table built, no workspace.
+template <typename T>
+int slice_at_impl(plx_lattice *L, const T *d_values, int vd, const int32_t *d_vid, const float *d_w, int64_t nq, T *d_out,
+                  hipStream_t stream);
 
 // contiguous near-equal row blocks: the first n % shards blocks get one extra row
 inline void shard_range(int64_t n, int shards, int index, int64_t *lo, int64_t *hi)

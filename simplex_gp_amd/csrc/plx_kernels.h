@@ -1,7 +1,8 @@
 // plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
 // plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip,
 // plx_rows_f64.hip, plx_backward_f64.hip, through plx_rows_backward_kernels.h plx_rows_backward.hip and
-// plx_rows_backward_f64.hip, and through plx_diag_kernels.h plx_diag.hip and plx_diag_f64.hip).  Not part of the C ABI.
+// plx_rows_backward_f64.hip, through plx_diag_kernels.h plx_diag.hip and plx_diag_f64.hip, and through plx_query_kernels.h
+// plx_query.hip and plx_query_f64.hip).  Not part of the C ABI.
 //
 // Reference: cpp/permutohedral.h ("h") splat value accumulation h:478-479,
 // blur h:513-572, slice h:497-510.  The reference's CUDA path does the splat
@@ -124,13 +125,23 @@ __device__ __forceinline__ double2 f64_vertex_sum(const int *__restrict__ row, c
     return acc;
 }
 
-// sum_r w_r values[v_r][ch] in corner order, then ONE division by 1 + 2^-d
+// sum_r w_r values[v_r][ch] in corner order, then ONE division by 1 + 2^-d.  SKIP (the slices at located queries,
+// plx_query_kernels.h): a corner whose id is negative is absent and contributes nothing -- skipped, not multiplied by zero;
+// without it, the present behaviour: every id is a vertex.
+template <bool SKIP = false>
 __device__ __forceinline__ double2 f64_point_sum(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
                                                  int d1, const double2 *__restrict__ values, int nch, int ch, double denom)
 {
     double2 acc = VecOps<double2>::zero();
-    for (int r = 0; r < d1; ++r)
-        VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)evid[(size_t)r * n + p] * nch + ch]);
+    for (int r = 0; r < d1; ++r) {
+        if constexpr (SKIP) {
+            const int v = evid[(size_t)r * n + p];
+            if (v < 0) continue;
+            VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)v * nch + ch]);
+        } else {
+            VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], values[(size_t)evid[(size_t)r * n + p] * nch + ch]);
+        }
+    }
     return make_double2(acc.x / denom, acc.y / denom);
 }
 
@@ -229,12 +240,16 @@ __device__ __forceinline__ void rows_term(float4 &acc, float w, float4 g, float 
 }
 
 // sum_r w_r values[v_r][ch] rden, in corner order, every term multiplied by the rounded reciprocal as plx_slice.hip does
+// SKIP: as for f64_point_sum
+template <bool SKIP = false>
 __device__ __forceinline__ float4 rows_point_sum(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
                                                  int d1, const float4 *__restrict__ values, int nch, int ch, float rden)
 {
     float4 acc = f4_zero();
     for (int r = 0; r < d1; ++r) {
         const int v = evid[(size_t)r * n + p];
+        if constexpr (SKIP)
+            if (v < 0) continue;
         const float wr = ew[(size_t)r * n + p];
         const float4 g = values[(size_t)v * nch + ch];
         rows_term(acc, wr, g, rden);
@@ -244,7 +259,7 @@ __device__ __forceinline__ float4 rows_point_sum(const int *__restrict__ evid, c
 
 // chunk ch of the filtered row of point p.  D1 > 0: d + 1 compiled in (all index / weight loads, then all gathers, then the
 // ordered sum); 0: the run-time form
-template <int D1>
+template <int D1, bool SKIP = false>
 __device__ __forceinline__ float4 rows_filtered_chunk(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
                                                       int d1, const float4 *__restrict__ values, int nch, int ch, float rden)
 {
@@ -258,13 +273,21 @@ __device__ __forceinline__ float4 rows_filtered_chunk(const int *__restrict__ ev
             v[r] = evid[(size_t)r * n + p];
             wr[r] = ew[(size_t)r * n + p];
         }
+        if constexpr (SKIP) {
 #pragma unroll
-        for (int r = 0; r < D1; ++r) g[r] = values[(size_t)v[r] * nch + ch];
+            for (int r = 0; r < D1; ++r) g[r] = v[r] >= 0 ? values[(size_t)v[r] * nch + ch] : f4_zero();
 #pragma unroll
-        for (int r = 0; r < D1; ++r) rows_term(acc, wr[r], g[r], rden);
+            for (int r = 0; r < D1; ++r)
+                if (v[r] >= 0) rows_term(acc, wr[r], g[r], rden);
+        } else {
+#pragma unroll
+            for (int r = 0; r < D1; ++r) g[r] = values[(size_t)v[r] * nch + ch];
+#pragma unroll
+            for (int r = 0; r < D1; ++r) rows_term(acc, wr[r], g[r], rden);
+        }
         return acc;
     } else {
-        return rows_point_sum(evid, ew, n, p, d1, values, nch, ch, rden);
+        return rows_point_sum<SKIP>(evid, ew, n, p, d1, values, nch, ch, rden);
     }
 }
 

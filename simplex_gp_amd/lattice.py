@@ -48,6 +48,17 @@ def _positions_f32(ref, name="ref"):
     return ref if ref.dtype == torch.float32 else ref.to(torch.float32)
 
 
+class LatticeQuery:
+    """Where nq points that are not the build's sit in a built lattice (Lattice.locate): vid [d+1, nq] int32, the vertex id
+    of every simplex corner in the numbering of build `build_id` of that lattice, -1 where the corner is not one of its
+    vertices; weight [d+1, nq] float32, the barycentric weights; mass [nq] float32 (None when not asked for), the sum of
+    the weights of the corners found: 1 where the whole simplex exists, 0 where the lattice knows nothing of the point."""
+    __slots__ = ("vid", "weight", "mass", "nq", "build_id")
+
+    def __init__(self, vid, weight, mass, nq, build_id):
+        self.vid, self.weight, self.mass, self.nq, self.build_id = vid, weight, mass, int(nq), int(build_id)
+
+
 class Lattice:
     """One permutohedral lattice on one GPU.
 
@@ -647,6 +658,89 @@ class Lattice:
                                        _stream_ptr(self.device))
         nv.check(rc, fn)
         return out
+
+    # -- queries at points that are not the build's (plx_locate / plx_slice_at) ---
+    # The operator is K_q(x*, X) = S* B_d ... B_0 S_X^T / (1 + 2^-d): S* holds a query's barycentric weights on those of its
+    # d + 1 corners that are vertices of X's lattice, an absent corner contributes nothing.  It is NOT the stacked operator of
+    # apply_rows on [x*; X], whose blur also runs through vertices that only the query points create; LatticeQuery.mass says
+    # how much of every query this lattice supports.
+    @staticmethod
+    def _need_query_symbols(who, *names):
+        for name in names:
+            if not nv.has_symbols(name):
+                raise RuntimeError(f"{who}: this libplx.so does not export {name}: rebuild it (make -C simplex_gp_amd/csrc)")
+
+    def locate(self, x, want_mass=True):
+        """The corners of the points x [nq, d] (CUDA float32, in the units of the build's positions: already divided by the
+        lengthscale; float64 is rounded to float32 as the build does) in this build's vertex numbering: a LatticeQuery.  One
+        launch, no workspace: graph-capturable.  Points outside the key range (or NaN / Inf) find nothing: mass 0."""
+        self._need_query_symbols("locate", "plx_locate")
+        x = _positions_f32(x, "x")
+        if x.shape[1] != self.d or x.shape[0] < 1:
+            raise ValueError(f"x must be [nq >= 1, {self.d}], got shape {tuple(x.shape)}")
+        if x.device != self.device:
+            raise ValueError(f"x is on {x.device}, the lattice on {self.device}")
+        x = x.contiguous()
+        nq, d1 = x.shape[0], self.d + 1
+        vid = torch.empty((d1, nq), dtype=torch.int32, device=self.device)
+        weight = torch.empty((d1, nq), dtype=torch.float32, device=self.device)
+        mass = torch.empty(nq, dtype=torch.float32, device=self.device) if want_mass else None
+        with torch.cuda.device(self.device):
+            rc = nv.lib().plx_locate(self._h, ctypes.c_void_p(x.data_ptr()), nq, ctypes.c_void_p(vid.data_ptr()),
+                                     ctypes.c_void_p(weight.data_ptr()),
+                                     ctypes.c_void_p(mass.data_ptr()) if want_mass else None, _stream_ptr(self.device))
+        nv.check(rc, "plx_locate")
+        return LatticeQuery(vid, weight, mass, nq, self.build_id)
+
+    def slice_at(self, values, query, out=None, vd=None):
+        """out[nq, vd] = S* values / (1 + 2^-d) at the located `query`, in the dtype of `values` (a vertex array
+        [>= m, values_stride(vd, dtype)], e.g. what blurred() returns).  A query located before the lattice's last build is
+        refused: its vertex ids belong to another numbering."""
+        if not isinstance(query, LatticeQuery):
+            raise TypeError(f"query must be a LatticeQuery (Lattice.locate), got {type(query).__name__}")
+        _check_f32_cuda(values, "values", f64_ok=True)
+        f64 = values.dtype == torch.float64
+        fn = "plx_slice_at_f64" if f64 else "plx_slice_at"
+        self._need_query_symbols("slice_at", fn)
+        if query.build_id != self.build_id:
+            raise RuntimeError(f"slice_at: the lattice was rebuilt since this query was located (build {query.build_id}, now "
+                               f"{self.build_id}): locate the points again")
+        vd = values.shape[1] if vd is None else int(vd)
+        if vd < 1 or values.shape[1] != self.values_stride(vd, values.dtype) or not values.is_contiguous():
+            raise ValueError(f"values must be contiguous [m, {self.values_stride(max(vd, 1), values.dtype)}] for vd = {vd}, "
+                             f"got shape {tuple(values.shape)}")
+        if values.shape[0] < self.m:
+            raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
+        if values.device != self.device or query.vid.device != self.device:
+            raise ValueError(f"values and query must be on {self.device}")
+        if out is None:
+            out = torch.empty((query.nq, vd), dtype=values.dtype, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != values.dtype:
+            raise TypeError(f"out must be a {values.dtype} tensor like values")
+        elif out.shape != (query.nq, vd) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be contiguous [{query.nq}, {vd}] on {self.device}")
+        with torch.cuda.device(self.device):
+            rc = getattr(nv.lib(), fn)(self._h, ctypes.c_void_p(values.data_ptr()), vd, ctypes.c_void_p(query.vid.data_ptr()),
+                                       ctypes.c_void_p(query.weight.data_ptr()), query.nq, ctypes.c_void_p(out.data_ptr()),
+                                       _stream_ptr(self.device))
+        nv.check(rc, fn)
+        return out
+
+    def blurred(self, src):
+        """(values, vd): splat + blur of src [n, vd] in its dtype, `values` being whichever buffer holds the result -- what
+        slice_at() reads.  It does not depend on any query: compute it once, slice it anywhere."""
+        values = self.splat(src)
+        return self.blur(values, vd=src.shape[1]), src.shape[1]
+
+    def apply_at(self, src, query):
+        """K_q(x*, X) src at the located query: slice_at(blurred(src), query)."""
+        values, vd = self.blurred(src)
+        return self.slice_at(values, query, vd=vd)
+
+    def query_kernels(self):
+        """Kernels launched by the last locate / slice_at on this lattice: {"locate": [...], "slice_at": [...]}."""
+        self._need_query_symbols("query_kernels", "plx_last_query_kernels")
+        return self._last_kernels("plx_last_query_kernels", 256)
 
     # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
     def _rows(self, begin, count):

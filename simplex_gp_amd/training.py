@@ -238,9 +238,58 @@ class PredictionCache:
             jitter = 1e-6 * T.diagonal().abs().max()
             self.chol = torch.linalg.cholesky(T + jitter * torch.eye(T.shape[0], dtype=T.dtype, device=T.device))
 
+    # Class switch, off: predict() takes route="stacked" unless told otherwise.  route="query" slices the training lattice
+    # at the test points (Lattice.locate + slice_at) instead of building a stacked lattice over [x*; X] per batch: the
+    # columns [alpha, Q] are splatted and blurred ONCE on the lattice model.kernel(x, x) was solved on, and a batch costs a
+    # locate and one slice.  The operator differs from the stacked one: K_q(x*, X) = S* B S_X^T / (1 + 2^-d) keeps only the
+    # corners of a test point that are vertices of the TRAINING lattice (an absent corner contributes nothing), where the
+    # stacked lattice also blurs through vertices the test points create.  last_query_mass says, per test row, how much of
+    # its barycentric weight the training lattice holds (1: the whole simplex; small: the route does not serve that row).
+    query_route = False
+
+    def _query_state(self):
+        """(lattice, blurred [alpha, Q] values, columns) for route="query", or None where that route is not served (off the
+        HIP path, a CPU model, a lattice the rows calls refuse): the blurred values are computed on first use, in the
+        model's dtype, and again whenever the lattice has been rebuilt since (its build_id moved)."""
+        from . import lattice_kernel as lk
+        from . import _native as nv
+        x = self.x
+        if lk.LatticeFilterGeneral.method is not None or not x.is_cuda or x.dtype not in (torch.float32, torch.float64):
+            return None
+        if not nv.has_symbols("plx_locate", "plx_slice_at", "plx_slice_at_f64"):
+            return None
+        st = self.__dict__.get("_query")
+        if st is not None and st[0].build_id == st[3]:
+            return st
+        K = self.model.kernel(x, x)                       # the operator __init__ solved on: the lattice cache serves its lattice
+        if not isinstance(K, lk.SquareLazyLattice):
+            return None
+        ref = lk.carry_hint(K.x.detach(), K.x)
+        ref = ref if ref.is_contiguous() else lk.carry_hint(ref.contiguous(), ref)
+        lat = lk.lattice_cache().get(ref, self.model.kernel.dkernel_fn.get_coeffs())
+        if not lat.accepts_rows():
+            return None
+        cols = self.alpha if self.Q is None else torch.cat([self.alpha, self.Q], 1)
+        lat.set_lattice_row_order(False)
+        values, vd = lat.blurred(cols.to(x.dtype).contiguous())
+        self._query = (lat, values, vd, lat.build_id)
+        return self._query
+
     @torch.no_grad()
-    def predict(self, x_star):
+    def predict(self, x_star, route=None):
+        """route: "stacked" (the rectangular operator on a lattice over [x*; X], built per batch), "query" (the training
+        lattice sliced at x*: see query_route), None = what the class switch says.  "query" falls through to "stacked"
+        wherever it is not served."""
+        if route is None:
+            route = "query" if self.query_route else "stacked"
+        if route not in ("stacked", "query"):
+            raise ValueError(f"route must be 'stacked', 'query' or None, got {route!r}")
         model = self.model
+        self.last_query_mass = None
+        if route == "query":
+            st = self._query_state()
+            if st is not None:
+                return self._predict_query(x_star, st)
         K_star = model.kernel(x_star, self.x)             # RectangularLazyLattice, [n*, n]
         s = model.outputscale
         if self.Q is None:
@@ -252,9 +301,25 @@ class PredictionCache:
         prior = s * model.kernel(x_star, x_star, diag=True)
         return mean, (prior - (proj ** 2).sum(0)).clamp_min(1e-8)
 
+    def _predict_query(self, x_star, st):
+        """predict() with K(x*, X) [alpha, Q] read off the blurred training lattice: the same triangular solve and prior."""
+        model = self.model
+        lat, values, vd, _ = st
+        query = lat.locate(x_star.div(model.kernel.lengthscale))
+        self.last_query_mass = query.mass
+        s = model.outputscale
+        KAQ = s * lat.slice_at(values, query, vd=vd)                                       # [n*, 1 + t]
+        mean = model.mean + KAQ[:, 0]
+        if self.Q is None:
+            return mean, None
+        proj = torch.linalg.solve_triangular(self.chol, KAQ[:, 1:].t(), upper=False)
+        prior = s * model.kernel(x_star, x_star, diag=True)
+        return mean, (prior - (proj ** 2).sum(0)).clamp_min(1e-8)
+
 
 @torch.no_grad()
-def predict(model, x, y, x_star, max_cg_iter=1000, cg_tol=1e-2, lanc_iter=100, variance=True, pre_size=100, cache=None):
+def predict(model, x, y, x_star, max_cg_iter=1000, cg_tol=1e-2, lanc_iter=100, variance=True, pre_size=100, cache=None,
+            route=None):
     """Posterior mean and variance of the latent function at x_star.
 
     mean = mu + s K(x*, X) (s K + sigma^2 I)^-1 (y - mu)          one CG solve + one rectangular MVM
@@ -263,11 +328,12 @@ def predict(model, x, y, x_star, max_cg_iter=1000, cg_tol=1e-2, lanc_iter=100, v
     pre_size: rank of the pivoted-Cholesky preconditioner of the mean solve (the reference's test() default,
     train_simplexgp.py:60: 100; 0 = plain CG)
     cache: a PredictionCache of (model, x, y) to predict from (the solve and the Lanczos run are then not repeated)
+    route: PredictionCache.predict's ("stacked", "query" or None = the class switch PredictionCache.query_route)
     """
     if cache is None:
         cache = PredictionCache(model, x, y, max_cg_iter=max_cg_iter, cg_tol=cg_tol, lanc_iter=lanc_iter, variance=variance,
                                 pre_size=pre_size)
-    return cache.predict(x_star)
+    return cache.predict(x_star, route=route)
 
 
 @torch.no_grad()
