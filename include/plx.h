@@ -386,8 +386,10 @@ int plx_apply_affine_f64(plx_lattice *lat, const double *d_src, int vd, double *
  *   plx_blur_t_f64        the adjoint of plx_blur_f64, with its arguments: the kernels of plx_blur_f64, host code only.
  *   plx_apply_t_f64       splat -> blur_t -> slice: K^T d_src, on the workspace of plx_apply_f64.
  *   plx_blur_sym_f64      0.5 (blur(values) + blur_t(values)) in d + 1 launches, each advancing both chains
- *                         (f64_blur_dual_kernel): launch k takes the forward chain through axis k, the reverse chain
- *                         through axis d - k; the first reads the one input plane for both, the last stores the one mean.
+ *                         (reported as f64_blur_dual_kernel; a profiler shows blur_dual_kernel<double, ...>, the double
+ *                         instance of the template the fp32 form below shares, csrc/plx_sym_kernels.h): launch k takes the
+ *                         forward chain through axis k, the reverse chain through axis d - k; the first reads the one input
+ *                         plane for both, the last stores the one mean.
  *                         d_work: plx_blur_sym_work_doubles(lat, vd) doubles (min(d + 1, 3) planes of m * stride; -1 for
  *                         vd < 1 or an unbuilt lattice), 16-byte aligned for vd > 1, not overlapping d_values.  *d_result
  *                         is set on the host, without synchronisation, to d_values or to a plane of d_work: where the

@@ -674,54 +674,179 @@ int plx_last_f64_kernels(const plx_lattice *L, char *buf, int cap)
     return PLX_OK;
 }
 
-// ---- the transposed and symmetrised float64 products (kernels: plx_sym_f64.hip around those of plx_f64.hip) -------------
+// ---- the transposed and symmetrised products, fp32 and float64 (kernels: plx_sym_kernels.h, instantiated by plx_sym.hip
+// and plx_sym_f64.hip, around blur_axis_kernel of plx_blur.hip and the blur kernels of plx_f64.hip) -------------------------
 
-// The stage implementations name their kernels in the kn_f64_* fields: a transposed or symmetrised call moves what it
-// launched to the kn_sym_* fields and leaves plx_last_f64_kernels with what the last plain call reported.
+// Everything a transposed or symmetrised fp32 call checks before any GPU work.  `a` / `b`: the call's two buffers.
+static int check_sym32(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
+{
+    PLX_TRY(check_call(L, a, b, vd, who));
+    PLX_TRY(check_plain_build(L, "the transposed and symmetrised products are", who));
+    return check_size(L, values_stride(vd), L->n, "n", who);
+}
+
+extern "C++" {      // one body per call for both types; the entry points below forward to them
+
+// The stage implementations name their kernels in the fields of the plain calls (kn_f64_*; kn_splat / kn_slice): a
+// transposed or symmetrised call moves what it launched to its own fields (kn_sym_*; kn_sym32_*) and leaves
+// plx_last_f64_kernels / plx_last_kernels with what the last plain call reported.  `blur`: the name of the blur where no
+// stage assigns one -- the dual kernel's, and in fp32 the transposed blur's too: nothing these calls run assigns kn_blur,
+// which is not borrowed (a NULL field).
+using KnField = const char *plx_lattice::*;
 struct SymKernelNames {
     plx_lattice *L;
-    const char *splat, *blur, *slice;
-    explicit SymKernelNames(plx_lattice *lat) : L(lat), splat(lat->kn_f64_splat), blur(lat->kn_f64_blur), slice(lat->kn_f64_slice)
+    const KnField *plain, *sym;      // splat, blur, slice
+    const char *saved[3] = {};
+    SymKernelNames(plx_lattice *lat, const KnField *plain_, const KnField *sym_, const char *blur) : L(lat), plain(plain_), sym(sym_)
     {
-        L->kn_f64_splat = L->kn_f64_blur = L->kn_f64_slice = L->kn_sym_splat = L->kn_sym_blur = L->kn_sym_slice = "";
+        for (int i = 0; i < 3; ++i) {
+            L->*sym[i] = "";
+            if (!plain[i]) continue;
+            saved[i] = L->*plain[i];
+            L->*plain[i] = "";
+        }
+        L->*sym[1] = blur;
     }
     ~SymKernelNames()
     {
-        if (*L->kn_f64_splat) L->kn_sym_splat = L->kn_f64_splat;
-        if (*L->kn_f64_blur) L->kn_sym_blur = L->kn_f64_blur;
-        if (*L->kn_f64_slice) L->kn_sym_slice = L->kn_f64_slice;
-        L->kn_f64_splat = splat;
-        L->kn_f64_blur = blur;
-        L->kn_f64_slice = slice;
+        for (int i = 0; i < 3; ++i) {
+            if (!plain[i]) continue;
+            if (*(L->*plain[i])) L->*sym[i] = L->*plain[i];
+            L->*plain[i] = saved[i];
+        }
     }
 };
 
+template <typename T> static bool overlap(const T *a, int64_t na, const T *b, int64_t nb)
+{
+    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
+
+// What the two types differ in here: the argument check, the workspace, the stage implementations, the name fields and
+// the names, and the aliasing rule of the transposed blur.
+template <typename T> struct SymHost;
+template <> struct SymHost<double> {
+    static constexpr KnField kPlain[3] = {&plx_lattice::kn_f64_splat, &plx_lattice::kn_f64_blur, &plx_lattice::kn_f64_slice};
+    static constexpr KnField kSym[3] = {&plx_lattice::kn_sym_splat, &plx_lattice::kn_sym_blur, &plx_lattice::kn_sym_slice};
+    static constexpr const char *kBlurT = "", *kDual = "f64_blur_dual_kernel", *kWorkSize = "plx_blur_sym_work_doubles";
+    static constexpr const char *kScratchRule = "must be different buffers";      // plx_blur_t_f64 refuses d_values == d_scratch only
+    static constexpr bool kScratchMayOverlap = true;
+    static constexpr DevBuf plx_lattice::*kValA = &plx_lattice::val64_a, plx_lattice::*kValB = &plx_lattice::val64_b,
+                                        plx_lattice::*kValS = &plx_lattice::val64_s;      // a, b: the workspace of plx_apply_f64
+    static constexpr auto check = check_f64; static constexpr auto stride = values_stride_f64;
+    static constexpr auto splat = splat_f64_impl; static constexpr auto slice = slice_f64_impl;
+    static constexpr auto blur_t = blur_t_f64_impl; static constexpr auto blur_sym = blur_sym_f64_impl;
+};
+template <> struct SymHost<float> {
+    static constexpr KnField kPlain[3] = {&plx_lattice::kn_splat, nullptr, &plx_lattice::kn_slice};
+    static constexpr KnField kSym[3] = {&plx_lattice::kn_sym32_splat, &plx_lattice::kn_sym32_blur, &plx_lattice::kn_sym32_slice};
+    static constexpr const char *kBlurT = "blur_axis_kernel", *kDual = "blur_dual_kernel", *kWorkSize = "plx_blur_sym_work_floats";
+    static constexpr const char *kScratchRule = "must not overlap";      // plx_blur_t refuses any overlap of the two planes
+    static constexpr bool kScratchMayOverlap = false;
+    static constexpr DevBuf plx_lattice::*kValA = &plx_lattice::val_a, plx_lattice::*kValB = &plx_lattice::val_b,
+                                        plx_lattice::*kValS = &plx_lattice::val_s;      // a, b: the workspace of plx_apply
+    static constexpr auto check = check_sym32; static constexpr auto stride = values_stride;
+    static constexpr auto blur_t = blur_t_impl; static constexpr auto blur_sym = blur_sym_impl;
+    static constexpr auto splat = splat_impl;      // (slice_impl has trailing arguments with defaults: a function of its own)
+    static int slice(plx_lattice *L, const float *d_values, int vd, float *d_out, hipStream_t s) { return slice_impl(L, d_values, vd, d_out, s); }
+};
+
+template <typename T>
+static int blur_t_entry(const char *who, plx_lattice *L, T *d_values, T *d_scratch, int vd, int *result_in_scratch, void *stream)
+{
+    using S = SymHost<T>;
+    EntryScope sc(L, stream);
+    PLX_TRY(S::check(L, d_values, d_scratch, vd, who));
+    if (!result_in_scratch) { set_error("%s: result_in_scratch is NULL", who); return PLX_ERR_INVALID; }
+    const int64_t plane = (int64_t)L->m * S::stride(vd);
+    if (S::kScratchMayOverlap ? d_values == d_scratch : overlap(d_values, plane, d_scratch, plane)) {
+        set_error("%s: d_values and d_scratch %s", who, S::kScratchRule);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, who));
+    PLX_TRY(check_values_aligned(d_scratch, vd, who));
+    DeviceGuard g(L->device);
+    SymKernelNames kn(L, S::kPlain, S::kSym, S::kBlurT);
+    return S::blur_t(L, d_values, d_scratch, vd, result_in_scratch, (hipStream_t)stream);
+}
+
+template <typename T> static int apply_t_entry(const char *who, plx_lattice *L, const T *d_src, int vd, T *d_out, void *stream)
+{
+    using S = SymHost<T>;
+    EntryScope sc(L, stream);
+    PLX_TRY(S::check(L, d_src, d_out, vd, who));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)L->m * S::stride(vd) * sizeof(T);
+    PLX_TRY(ensure(L->*S::kValA, bytes));
+    PLX_TRY(ensure(L->*S::kValB, bytes));
+    T *va = (L->*S::kValA).template as<T>(), *vb = (L->*S::kValB).template as<T>();
+    SymKernelNames kn(L, S::kPlain, S::kSym, S::kBlurT);
+    PLX_TRY(S::splat(L, d_src, vd, va, s));
+    int in_b = 0;
+    PLX_TRY(S::blur_t(L, va, vb, vd, &in_b, s));
+    return S::slice(L, in_b ? vb : va, vd, d_out, s);
+}
+
+template <typename T>
+static int blur_sym_entry(const char *who, plx_lattice *L, T *d_values, T *d_work, int vd, T **d_result, void *stream)
+{
+    using S = SymHost<T>;
+    EntryScope sc(L, stream);
+    PLX_TRY(S::check(L, d_values, d_work, vd, who));
+    if (!d_result) { set_error("%s: d_result is NULL", who); return PLX_ERR_INVALID; }
+    const int64_t plane = (int64_t)L->m * S::stride(vd);
+    if (overlap(d_values, plane, d_work, blur_sym_planes(L) * plane)) {
+        set_error("%s: d_values and d_work (%s) must not overlap", who, S::kWorkSize);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, who));
+    PLX_TRY(check_values_aligned(d_work, vd, who));
+    DeviceGuard g(L->device);
+    SymKernelNames kn(L, S::kPlain, S::kSym, S::kDual);
+    T *planes[3] = {d_work, d_work + plane, d_work + 2 * plane};      // (the last ones unused where d + 1 < 3)
+    return S::blur_sym(L, d_values, planes, vd, d_result, (hipStream_t)stream);
+}
+
+// splat + symmetrised blur on the lattice's workspace of the type: plane a holds the splat, plane b and the two planes of
+// val_s / val64_s are the work space; *d_blurred: the plane the slice reads
+template <typename T> static int splat_blur_sym(plx_lattice *L, const T *d_src, int vd, T **d_blurred, hipStream_t s)
+{
+    using S = SymHost<T>;
+    const size_t plane = (size_t)L->m * S::stride(vd);
+    PLX_TRY(ensure(L->*S::kValA, plane * sizeof(T)));
+    PLX_TRY(ensure(L->*S::kValB, plane * sizeof(T)));
+    PLX_TRY(ensure(L->*S::kValS, 2 * plane * sizeof(T)));
+    T *va = (L->*S::kValA).template as<T>(), *vs = (L->*S::kValS).template as<T>();
+    PLX_TRY(S::splat(L, d_src, vd, va, s));
+    // the three work planes need not be contiguous here: the symmetrised blur takes them one by one
+    T *planes[3] = {(L->*S::kValB).template as<T>(), vs, vs + plane};
+    return S::blur_sym(L, va, planes, vd, d_blurred, s);
+}
+
+template <typename T> static int apply_sym_entry(const char *who, plx_lattice *L, const T *d_src, int vd, T *d_out, void *stream)
+{
+    using S = SymHost<T>;
+    EntryScope sc(L, stream);
+    PLX_TRY(S::check(L, d_src, d_out, vd, who));
+    DeviceGuard g(L->device);
+    hipStream_t s = (hipStream_t)stream;
+    SymKernelNames kn(L, S::kPlain, S::kSym, S::kDual);
+    T *blurred = nullptr;
+    PLX_TRY(splat_blur_sym<T>(L, d_src, vd, &blurred, s));
+    return S::slice(L, blurred, vd, d_out, s);
+}
+
+}  // extern "C++"
+
 int plx_blur_t_f64(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_f64(L, d_values, d_scratch, vd, "plx_blur_t_f64"));
-    if (!result_in_scratch) { set_error("plx_blur_t_f64: result_in_scratch is NULL"); return PLX_ERR_INVALID; }
-    if (d_values == d_scratch) { set_error("plx_blur_t_f64: d_values and d_scratch must be different buffers"); return PLX_ERR_INVALID; }
-    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_t_f64"));
-    PLX_TRY(check_values_aligned(d_scratch, vd, "plx_blur_t_f64"));
-    DeviceGuard g(L->device);
-    SymKernelNames kn(L);
-    return blur_t_f64_impl(L, d_values, d_scratch, vd, result_in_scratch, (hipStream_t)stream);
+    return blur_t_entry<double>("plx_blur_t_f64", L, d_values, d_scratch, vd, result_in_scratch, stream);
 }
 
 int plx_apply_t_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_f64(L, d_src, d_out, vd, "plx_apply_t_f64"));
-    DeviceGuard g(L->device);
-    hipStream_t s = (hipStream_t)stream;
-    PLX_TRY(ensure(L->val64_a, (size_t)L->m * values_stride_f64(vd) * 8));      // the workspace of plx_apply_f64
-    PLX_TRY(ensure(L->val64_b, (size_t)L->m * values_stride_f64(vd) * 8));
-    SymKernelNames kn(L);
-    PLX_TRY(splat_f64_impl(L, d_src, vd, L->val64_a.as<double>(), s));
-    int in_b = 0;
-    PLX_TRY(blur_t_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), vd, &in_b, s));
-    return slice_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, d_out, s);
+    return apply_t_entry<double>("plx_apply_t_f64", L, d_src, vd, d_out, stream);
 }
 
 int64_t plx_blur_sym_work_doubles(const plx_lattice *L, int vd)
@@ -732,49 +857,12 @@ int64_t plx_blur_sym_work_doubles(const plx_lattice *L, int vd)
 
 int plx_blur_sym_f64(plx_lattice *L, double *d_values, double *d_work, int vd, double **d_result, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_f64(L, d_values, d_work, vd, "plx_blur_sym_f64"));
-    if (!d_result) { set_error("plx_blur_sym_f64: d_result is NULL"); return PLX_ERR_INVALID; }
-    const double *work_end = d_work + plx_blur_sym_work_doubles(L, vd), *values_end = d_values + (size_t)L->m * values_stride_f64(vd);
-    if (d_values < work_end && d_work < values_end) {
-        set_error("plx_blur_sym_f64: d_values and d_work (plx_blur_sym_work_doubles) must not overlap");
-        return PLX_ERR_INVALID;
-    }
-    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_sym_f64"));
-    PLX_TRY(check_values_aligned(d_work, vd, "plx_blur_sym_f64"));
-    DeviceGuard g(L->device);
-    SymKernelNames kn(L);
-    L->kn_f64_blur = "f64_blur_dual_kernel";
-    const size_t plane = (size_t)L->m * values_stride_f64(vd);
-    double *planes[3] = {d_work, d_work + plane, d_work + 2 * plane};      // (the last ones unused where d + 1 < 3)
-    return blur_sym_f64_impl(L, d_values, planes, vd, d_result, (hipStream_t)stream);
-}
-
-// splat + symmetrised blur on the lattice's fp64 workspace: val64_a holds the splat, val64_b and the two planes of val64_s
-// are the work space; *d_blurred: the plane the slice reads
-static int splat_blur_sym_f64(plx_lattice *L, const double *d_src, int vd, double **d_blurred, hipStream_t s)
-{
-    const size_t plane = (size_t)L->m * values_stride_f64(vd);
-    PLX_TRY(ensure(L->val64_a, plane * 8));      // the workspace of plx_apply_f64
-    PLX_TRY(ensure(L->val64_b, plane * 8));
-    PLX_TRY(ensure(L->val64_s, 2 * plane * 8));
-    PLX_TRY(splat_f64_impl(L, d_src, vd, L->val64_a.as<double>(), s));
-    // the three work planes need not be contiguous here: the symmetrised blur takes them one by one
-    L->kn_f64_blur = "f64_blur_dual_kernel";
-    double *planes[3] = {L->val64_b.as<double>(), L->val64_s.as<double>(), L->val64_s.as<double>() + plane};
-    return blur_sym_f64_impl(L, L->val64_a.as<double>(), planes, vd, d_blurred, s);
+    return blur_sym_entry<double>("plx_blur_sym_f64", L, d_values, d_work, vd, d_result, stream);
 }
 
 int plx_apply_sym_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_f64(L, d_src, d_out, vd, "plx_apply_sym_f64"));
-    DeviceGuard g(L->device);
-    hipStream_t s = (hipStream_t)stream;
-    SymKernelNames kn(L);
-    double *blurred = nullptr;
-    PLX_TRY(splat_blur_sym_f64(L, d_src, vd, &blurred, s));
-    return slice_f64_impl(L, blurred, vd, d_out, s);
+    return apply_sym_entry<double>("plx_apply_sym_f64", L, d_src, vd, d_out, stream);
 }
 
 int plx_apply_affine_sym_f64(plx_lattice *L, const double *d_src, int vd, double *d_out, const double *d_scale_shift, double *d_dot,
@@ -794,9 +882,9 @@ int plx_apply_affine_sym_f64(plx_lattice *L, const double *d_src, int vd, double
     }
     DeviceGuard g(L->device);
     hipStream_t s = (hipStream_t)stream;
-    SymKernelNames kn(L);
+    SymKernelNames kn(L, SymHost<double>::kPlain, SymHost<double>::kSym, SymHost<double>::kDual);
     double *blurred = nullptr;
-    PLX_TRY(splat_blur_sym_f64(L, d_src, vd, &blurred, s));
+    PLX_TRY(splat_blur_sym<double>(L, d_src, vd, &blurred, s));
     PLX_TRY(slice_affine_f64_impl(L, blurred, vd, d_src, d_scale_shift, d_out, d_dot ? d_work : nullptr, s));
     if (!d_dot) return PLX_OK;
     return coldot_final_f64(d_work, dot_rows, values_stride_f64(vd), vd, d_dot, s);
@@ -809,72 +897,15 @@ int plx_last_sym_f64_kernels(const plx_lattice *L, char *buf, int cap)
     return PLX_OK;
 }
 
-// ---- the transposed and symmetrised fp32 products (kernels: plx_sym.hip around blur_axis_kernel of plx_blur.hip) -------
-
-// splat_impl and slice_impl name their kernels in kn_splat / kn_slice: a transposed or symmetrised fp32 call moves what it
-// launched to the kn_sym32_* fields and leaves plx_last_kernels with what the last plain call reported.  (Nothing these
-// calls run assigns kn_blur.)
-struct Sym32KernelNames {
-    plx_lattice *L;
-    const char *splat, *slice;
-    Sym32KernelNames(plx_lattice *lat, const char *blur) : L(lat), splat(lat->kn_splat), slice(lat->kn_slice)
-    {
-        L->kn_splat = L->kn_slice = "";
-        L->kn_sym32_splat = L->kn_sym32_slice = "";
-        L->kn_sym32_blur = blur;
-    }
-    ~Sym32KernelNames()
-    {
-        if (*L->kn_splat) L->kn_sym32_splat = L->kn_splat;
-        if (*L->kn_slice) L->kn_sym32_slice = L->kn_slice;
-        L->kn_splat = splat;
-        L->kn_slice = slice;
-    }
-};
-
-// Everything a transposed or symmetrised fp32 call checks before any GPU work.  `a` / `b`: the call's two buffers.
-static int check_sym32(const plx_lattice *L, const void *a, const void *b, int vd, const char *who)
-{
-    PLX_TRY(check_call(L, a, b, vd, who));
-    PLX_TRY(check_plain_build(L, "the transposed and symmetrised products are", who));
-    return check_size(L, values_stride(vd), L->n, "n", who);
-}
-
-static bool floats_overlap(const float *a, int64_t na, const float *b, int64_t nb)
-{
-    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
-}
-
+// ... and the fp32 ones
 int plx_blur_t(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *result_in_scratch, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_sym32(L, d_values, d_scratch, vd, "plx_blur_t"));
-    if (!result_in_scratch) { set_error("plx_blur_t: result_in_scratch is NULL"); return PLX_ERR_INVALID; }
-    const int64_t plane = (int64_t)L->m * values_stride(vd);
-    if (floats_overlap(d_values, plane, d_scratch, plane)) {
-        set_error("plx_blur_t: d_values and d_scratch must not overlap");
-        return PLX_ERR_INVALID;
-    }
-    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_t"));
-    PLX_TRY(check_values_aligned(d_scratch, vd, "plx_blur_t"));
-    DeviceGuard g(L->device);
-    Sym32KernelNames kn(L, "blur_axis_kernel");
-    return blur_t_impl(L, d_values, d_scratch, vd, result_in_scratch, (hipStream_t)stream);
+    return blur_t_entry<float>("plx_blur_t", L, d_values, d_scratch, vd, result_in_scratch, stream);
 }
 
 int plx_apply_t(plx_lattice *L, const float *d_src, int vd, float *d_out, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_sym32(L, d_src, d_out, vd, "plx_apply_t"));
-    DeviceGuard g(L->device);
-    hipStream_t s = (hipStream_t)stream;
-    PLX_TRY(ensure(L->val_a, (size_t)L->m * values_stride(vd) * 4));      // the workspace of plx_apply
-    PLX_TRY(ensure(L->val_b, (size_t)L->m * values_stride(vd) * 4));
-    Sym32KernelNames kn(L, "blur_axis_kernel");
-    PLX_TRY(splat_impl(L, d_src, vd, L->val_a.as<float>(), s));
-    int in_b = 0;
-    PLX_TRY(blur_t_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), vd, &in_b, s));
-    return slice_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, d_out, s);
+    return apply_t_entry<float>("plx_apply_t", L, d_src, vd, d_out, stream);
 }
 
 int64_t plx_blur_sym_work_floats(const plx_lattice *L, int vd)
@@ -885,46 +916,12 @@ int64_t plx_blur_sym_work_floats(const plx_lattice *L, int vd)
 
 int plx_blur_sym(plx_lattice *L, float *d_values, float *d_work, int vd, float **d_result, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_sym32(L, d_values, d_work, vd, "plx_blur_sym"));
-    if (!d_result) { set_error("plx_blur_sym: d_result is NULL"); return PLX_ERR_INVALID; }
-    const int64_t plane = (int64_t)L->m * values_stride(vd);
-    if (floats_overlap(d_values, plane, d_work, plx_blur_sym_work_floats(L, vd))) {
-        set_error("plx_blur_sym: d_values and d_work (plx_blur_sym_work_floats) must not overlap");
-        return PLX_ERR_INVALID;
-    }
-    PLX_TRY(check_values_aligned(d_values, vd, "plx_blur_sym"));
-    PLX_TRY(check_values_aligned(d_work, vd, "plx_blur_sym"));
-    DeviceGuard g(L->device);
-    Sym32KernelNames kn(L, "blur_dual_kernel");
-    float *planes[3] = {d_work, d_work + plane, d_work + 2 * plane};      // (the last ones unused where d + 1 < 3)
-    return blur_sym_impl(L, d_values, planes, vd, d_result, (hipStream_t)stream);
-}
-
-// splat + symmetrised blur on the lattice's fp32 workspace: val_a holds the splat, val_b and the two planes of val_s are
-// the work space; *d_blurred: the plane the slice reads
-static int splat_blur_sym(plx_lattice *L, const float *d_src, int vd, float **d_blurred, hipStream_t s)
-{
-    const size_t plane = (size_t)L->m * values_stride(vd);
-    PLX_TRY(ensure(L->val_a, plane * 4));      // the workspace of plx_apply
-    PLX_TRY(ensure(L->val_b, plane * 4));
-    PLX_TRY(ensure(L->val_s, 2 * plane * 4));
-    PLX_TRY(splat_impl(L, d_src, vd, L->val_a.as<float>(), s));
-    // the three work planes need not be contiguous here: the symmetrised blur takes them one by one
-    float *planes[3] = {L->val_b.as<float>(), L->val_s.as<float>(), L->val_s.as<float>() + plane};
-    return blur_sym_impl(L, L->val_a.as<float>(), planes, vd, d_blurred, s);
+    return blur_sym_entry<float>("plx_blur_sym", L, d_values, d_work, vd, d_result, stream);
 }
 
 int plx_apply_sym(plx_lattice *L, const float *d_src, int vd, float *d_out, void *stream)
 {
-    EntryScope sc(L, stream);
-    PLX_TRY(check_sym32(L, d_src, d_out, vd, "plx_apply_sym"));
-    DeviceGuard g(L->device);
-    hipStream_t s = (hipStream_t)stream;
-    Sym32KernelNames kn(L, "blur_dual_kernel");
-    float *blurred = nullptr;
-    PLX_TRY(splat_blur_sym(L, d_src, vd, &blurred, s));
-    return slice_impl(L, blurred, vd, d_out, s);
+    return apply_sym_entry<float>("plx_apply_sym", L, d_src, vd, d_out, stream);
 }
 
 int plx_apply_affine_sym(plx_lattice *L, const float *d_src, int vd, float *d_out, const float *d_scale_shift, float *d_dot,
@@ -941,9 +938,9 @@ int plx_apply_affine_sym(plx_lattice *L, const float *d_src, int vd, float *d_ou
     }
     DeviceGuard g(L->device);
     hipStream_t s = (hipStream_t)stream;
-    Sym32KernelNames kn(L, "blur_dual_kernel");
+    SymKernelNames kn(L, SymHost<float>::kPlain, SymHost<float>::kSym, SymHost<float>::kDual);
     float *blurred = nullptr;
-    PLX_TRY(splat_blur_sym(L, d_src, vd, &blurred, s));
+    PLX_TRY(splat_blur_sym<float>(L, d_src, vd, &blurred, s));
     PLX_TRY(slice_impl(L, blurred, vd, d_out, s, d_scale_shift, d_src, d_work));
     if (!d_dot) return PLX_OK;          // d_work set: the per-tile partial sums stay there (plx_cg_step_update_fused adds them up)
     return coldot_final(d_work, affine_dot_tiles(L, vd), values_stride(vd), d_dot, s);

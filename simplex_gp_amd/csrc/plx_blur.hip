@@ -729,7 +729,7 @@ static void launch_blur_general(const V *cur, V *nxt, const int *nb, int m, int6
     }
 }
 
-// One axis through the general family with the taps given (plx_sym.hip: the transposed blur runs the axes in reverse with
+// One axis through the general family with the taps given (plx_sym_kernels.h: the transposed blur runs the axes in reverse with
 // mirrored taps).  Names no kernel: the caller reports what it launched.
 void blur_axis_general(plx_lattice *L, const float *cur, float *nxt, int axis, int vd, const TapArgs &taps, hipStream_t stream)
 {

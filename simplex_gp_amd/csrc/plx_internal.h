@@ -305,12 +305,12 @@ struct plx_lattice {
     hipEvent_t tev[PLX_MAX_DIM + 8] = {};
     int tev_n = 0;
 
-    // the transposed and symmetrised float64 products (plx_sym_f64.hip): the two further value planes of the symmetrised
+    // the transposed and symmetrised float64 products (plx_sym_kernels.h): the two further value planes of the symmetrised
     // blur, allocated by the first plx_apply_sym_f64 of a width, and the kernels of the last such call
     plx::DevBuf val64_s;                      // double [2][m][plx_values_stride_f64(vd)]
     const char *kn_sym_splat = "", *kn_sym_blur = "", *kn_sym_slice = "";   // plx_last_sym_f64_kernels
 
-    // ... and the fp32 ones (plx_sym.hip): the two further planes of plx_apply_sym beside val_a / val_b, allocated by the
+    // ... and the fp32 ones: the two further planes of plx_apply_sym beside val_a / val_b, allocated by the
     // first such call of a width, and the kernels of the last transposed or symmetrised fp32 call
     plx::DevBuf val_s;                        // float [2][m][plx_values_stride(vd)]
     const char *kn_sym32_splat = "", *kn_sym32_blur = "", *kn_sym32_slice = "";   // plx_last_sym_kernels
@@ -387,10 +387,10 @@ int slice_impl(plx_lattice *L, const float *d_values, int vd, float *d_out, hipS
 // plx_blur.hip: one axis of the blur through the general family (blur_axis_kernel) with the taps given: nxt = B_axis cur
 // (cur != nxt).  Assigns no kernel name.
 void blur_axis_general(plx_lattice *L, const float *cur, float *nxt, int axis, int vd, const TapArgs &taps, hipStream_t stream);
-// plx_sym.hip: the transposed fp32 blur (axes d .. 0, mirrored taps, blur_axis_general) and the symmetrised one,
-// 0.5f (blur + blur_t) with the general family's bits, both chains advanced by each of d + 1 launches.  blur_sym_planes:
-// planes of m * stride floats the symmetrised blur needs beside d_values (1, 2 or 3 of d_work[], in that order);
-// *d_result: d_values or one of them.
+// plx_sym_kernels.h with T = float (plx_sym.hip): the transposed fp32 blur (axes d .. 0, mirrored taps, blur_axis_general)
+// and the symmetrised one, 0.5f (blur + blur_t) with the general family's bits, both chains advanced by each of d + 1
+// launches.  blur_sym_planes: planes of m * stride floats the symmetrised blur needs beside d_values (1, 2 or 3 of d_work[],
+// in that order); *d_result: d_values or one of them.
 int blur_t_impl(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
 int blur_sym_planes(const plx_lattice *L);
 int blur_sym_impl(plx_lattice *L, float *d_values, float *const d_work[3], int vd, float **d_result, hipStream_t stream);
@@ -415,9 +415,9 @@ int blur_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, i
 int slice_f64_impl(plx_lattice *L, const double *d_values, int vd, double *d_out, hipStream_t stream);
 // ... and one axis of the blur with the taps given: out = B_axis old (old != out), the launch blur_f64_impl makes per axis
 void blur_axis_f64(plx_lattice *L, const double *old, double *out, int axis, int vd, const TapArgs64 &taps, hipStream_t stream);
-// plx_sym_f64.hip: the transposed blur (axes d .. 0, mirrored taps, the kernels of plx_f64.hip) and the symmetrised one,
-// 0.5 (blur + blur_t), both chains advanced by each of d + 1 launches.  blur_sym_f64_planes: planes of m * stride doubles
-// the symmetrised blur needs beside d_values (1, 2 or 3 of d_work[], in that order); *d_result: d_values or one of them.
+// plx_sym_kernels.h with T = double (plx_sym_f64.hip): the transposed blur (axes d .. 0, mirrored taps, the kernels of
+// plx_f64.hip) and the symmetrised one, 0.5 (blur + blur_t), both chains advanced by each of d + 1 launches.
+// blur_sym_f64_planes: the same count as blur_sym_planes, of planes of m * stride doubles; *d_result: d_values or one of them.
 int blur_t_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
 int blur_sym_f64_planes(const plx_lattice *L);
 int blur_sym_f64_impl(plx_lattice *L, double *d_values, double *const d_work[3], int vd, double **d_result, hipStream_t stream);

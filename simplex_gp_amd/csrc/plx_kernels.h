@@ -1,8 +1,9 @@
 // plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
 // plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip,
 // plx_rows_f64.hip, plx_backward_f64.hip, through plx_rows_backward_kernels.h plx_rows_backward.hip and
-// plx_rows_backward_f64.hip, through plx_diag_kernels.h plx_diag.hip and plx_diag_f64.hip, and through plx_query_kernels.h
-// plx_query.hip and plx_query_f64.hip).  Not part of the C ABI.
+// plx_rows_backward_f64.hip, through plx_sym_kernels.h plx_sym.hip and plx_sym_f64.hip, through plx_diag_kernels.h
+// plx_diag.hip and plx_diag_f64.hip, and through plx_query_kernels.h plx_query.hip and plx_query_f64.hip).  Not part of
+// the C ABI.
 //
 // Reference: cpp/permutohedral.h ("h") splat value accumulation h:478-479,
 // blur h:513-572, slice h:497-510.  The reference's CUDA path does the splat

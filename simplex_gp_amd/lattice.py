@@ -434,21 +434,27 @@ class Lattice:
     def blur_t(self, values, scratch=None, vd=None):
         """The adjoint of the float64 blur(): axes d .. 0, mirrored taps (plx_blur_t_f64).  Returns the tensor that holds
         the result (either `values` or `scratch`), as blur() does."""
-        self._f64_only(values, "values", "blur_t")
-        _check_f32_cuda(values, "values", f64_ok=True)
+        return self._blur_t(torch.float64, "plx_blur_t_f64", lambda t, name: self._f64_only(t, name, "blur_t"),
+                            "buffer of the values' dtype", values, scratch, vd)
+
+    def _blur_t(self, dtype, symbol, refuse, scratch_is, values, scratch, vd):
+        """The body of blur_t (float64) and blur_t_f32 (float32): `symbol` is the library's call for `dtype`, `refuse`
+        the public method's refusal of the other dtype, `scratch_is` its words for the scratch buffer."""
+        refuse(values, "values")
+        _check_f32_cuda(values, "values", f64_ok=dtype == torch.float64)
         vd = values.shape[1] if vd is None else vd
-        assert values.shape[1] == self.values_stride(vd, values.dtype) and values.is_contiguous()
+        assert values.shape[1] == self.values_stride(vd, dtype) and values.is_contiguous()
         if values.shape[0] < self.m:
             raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
         if scratch is None:
             scratch = torch.empty_like(values)
         elif scratch.numel() < values.numel() or not scratch.is_contiguous() or scratch.dtype != values.dtype:
-            raise ValueError("scratch must be a contiguous buffer of the values' dtype, at least as large as values")
+            raise ValueError(f"scratch must be a contiguous {scratch_is}, at least as large as values")
         flag = ctypes.c_int(0)
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_blur_t_f64(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), vd,
-                                         ctypes.byref(flag), _stream_ptr(self.device))
-        nv.check(rc, "plx_blur_t_f64")
+            rc = getattr(nv.lib(), symbol)(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), vd,
+                                           ctypes.byref(flag), _stream_ptr(self.device))
+        nv.check(rc, symbol)
         return scratch if flag.value else values
 
     def blur_sym(self, values, work=None, vd=None):
@@ -456,52 +462,68 @@ class Lattice:
         [m, values_stride(vd)] float64 is clobbered; `work`: a contiguous float64 buffer of at least
         plx_blur_sym_work_doubles elements (allocated when None).  Returns an [m, stride] tensor that views `values` or
         `work`, wherever the result lies."""
-        self._f64_only(values, "values", "blur_sym")
-        _check_f32_cuda(values, "values", f64_ok=True)
+        return self._blur_sym(torch.float64, "plx_blur_sym_f64", "plx_blur_sym_work_doubles", "blur_sym",
+                              lambda t, name: self._f64_only(t, name, "blur_sym"), values, work, vd)
+
+    def _blur_sym(self, dtype, symbol, work_symbol, what, refuse, values, work, vd):
+        """The body of blur_sym (float64) and blur_sym_f32 (float32): `symbol` and `work_symbol` are the library's call and
+        its work-size function for `dtype`, `what` the public method's name, `refuse` its refusal of the other dtype."""
+        refuse(values, "values")
+        _check_f32_cuda(values, "values", f64_ok=dtype == torch.float64)
         vd = values.shape[1] if vd is None else vd
-        stride = self.values_stride(vd, values.dtype)
+        stride = self.values_stride(vd, dtype)
         assert values.shape[1] == stride and values.is_contiguous()
         if values.shape[0] < self.m:
             raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
-        need = int(nv.lib().plx_blur_sym_work_doubles(self._h, vd))
+        need = int(getattr(nv.lib(), work_symbol)(self._h, vd))
         if need < 0:
-            raise ValueError(f"blur_sym needs a built lattice and vd >= 1, got vd = {vd}")
+            raise ValueError(f"{what} needs a built lattice and vd >= 1, got vd = {vd}")
         if work is None:
-            work = torch.empty(need, dtype=torch.float64, device=self.device)
-        elif work.numel() < need or not work.is_contiguous() or work.dtype != torch.float64:
-            raise ValueError(f"work must be a contiguous float64 buffer of at least {need} elements")
+            work = torch.empty(need, dtype=dtype, device=self.device)
+        elif work.numel() < need or not work.is_contiguous() or work.dtype != dtype:
+            raise ValueError(f"work must be a contiguous {str(dtype).split('.')[-1]} buffer of at least {need} elements")
         res = ctypes.c_void_p(0)
         with torch.cuda.device(self.device):
-            rc = nv.lib().plx_blur_sym_f64(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(work.data_ptr()), vd,
+            rc = getattr(nv.lib(), symbol)(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(work.data_ptr()), vd,
                                            ctypes.byref(res), _stream_ptr(self.device))
-        nv.check(rc, "plx_blur_sym_f64")
+        nv.check(rc, symbol)
         if res.value == values.data_ptr():
             return values[:self.m]
-        off = (res.value - work.data_ptr()) // 8
+        off = (res.value - work.data_ptr()) // work.element_size()
         return work.view(-1)[off:off + self.m * stride].view(self.m, stride)
 
-    def _apply_f64_variant(self, src, out, fn, what):
-        self._f64_only(src, "src", what)
-        src = self._src(src, self.n_owned, f64_ok=True)
+    def _apply_variant(self, dtype, symbol, refuse, src, out):
+        """The body of apply_t / apply_sym (float64) and apply_t_f32 / apply_sym_f32 (float32): `symbol` is the library's
+        call for `dtype`, `refuse` the public method's refusal of the other dtype (fp32 refuses a float64 `out` up front;
+        float64 names the dtype of a wrong `out` after the checks of src)."""
+        f64 = dtype == torch.float64
+        refuse(src, "src")
+        if not f64:
+            refuse(out, "out")
+        _check_f32_cuda(src, "src", f64_ok=f64)
+        src = self._src(src, self.n_owned, f64_ok=f64)
         vd = src.shape[1]
         if out is None:
-            out = torch.empty((self.n_owned, vd), dtype=torch.float64, device=self.device)
+            out = torch.empty((self.n_owned, vd), dtype=dtype, device=self.device)
+        elif not f64:
+            _check_f32_cuda(out, "out")
         elif out.dtype != torch.float64:
             raise TypeError(f"out must be torch.float64 like src, got {out.dtype}")
         with torch.cuda.device(self.device):
-            rc = getattr(nv.lib(), fn)(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
-                                       _stream_ptr(self.device))
-        nv.check(rc, fn)
+            rc = getattr(nv.lib(), symbol)(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
+                                           _stream_ptr(self.device))
+        nv.check(rc, symbol)
         return out
 
     def apply_t(self, src, out=None):
         """out = K^T src: slice(blur_t(splat(src))) on the float64 workspace (plx_apply_t_f64).  float64 only."""
-        return self._apply_f64_variant(src, out, "plx_apply_t_f64", "apply_t")
+        return self._apply_variant(torch.float64, "plx_apply_t_f64", lambda t, name: self._f64_only(t, name, "apply_t"), src, out)
 
     def apply_sym(self, src, out=None):
         """out = K_s src with K_s = (K + K^T) / 2: slice(blur_sym(splat(src))) (plx_apply_sym_f64).  float64 only.  K_s is
         symmetric to rounding; it is not proven positive."""
-        return self._apply_f64_variant(src, out, "plx_apply_sym_f64", "apply_sym")
+        return self._apply_variant(torch.float64, "plx_apply_sym_f64", lambda t, name: self._f64_only(t, name, "apply_sym"),
+                                   src, out)
 
     def sym_f64_kernels(self):
         """Kernels launched by the last transposed or symmetrised float64 call: {"splat": [...], "blur": [...],
@@ -520,76 +542,27 @@ class Lattice:
     def blur_t_f32(self, values, scratch=None, vd=None):
         """The adjoint of the fp32 blur(): axes d .. 0, mirrored taps, the general kernel family (plx_blur_t).  Returns the
         tensor that holds the result (either `values` or `scratch`), as blur() does."""
-        self._f32_only(values, "values", "blur_t_f32", "blur_t")
-        _check_f32_cuda(values, "values")
-        vd = values.shape[1] if vd is None else vd
-        assert values.shape[1] == self.values_stride(vd) and values.is_contiguous()
-        if values.shape[0] < self.m:
-            raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
-        if scratch is None:
-            scratch = torch.empty_like(values)
-        elif scratch.numel() < values.numel() or not scratch.is_contiguous() or scratch.dtype != values.dtype:
-            raise ValueError("scratch must be a contiguous float32 buffer, at least as large as values")
-        flag = ctypes.c_int(0)
-        with torch.cuda.device(self.device):
-            rc = nv.lib().plx_blur_t(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), vd,
-                                     ctypes.byref(flag), _stream_ptr(self.device))
-        nv.check(rc, "plx_blur_t")
-        return scratch if flag.value else values
+        return self._blur_t(torch.float32, "plx_blur_t", lambda t, name: self._f32_only(t, name, "blur_t_f32", "blur_t"),
+                            "float32 buffer", values, scratch, vd)
 
     def blur_sym_f32(self, values, work=None, vd=None):
         """0.5 * (blur(values) + blur_t_f32(values)) with the general family's bits, in d + 1 launches that advance both
         chains (plx_blur_sym).  `values` [m, values_stride(vd)] float32 is clobbered; `work`: a contiguous float32 buffer
         of at least plx_blur_sym_work_floats elements (allocated when None).  Returns an [m, stride] tensor that views
         `values` or `work`, wherever the result lies."""
-        self._f32_only(values, "values", "blur_sym_f32", "blur_sym")
-        _check_f32_cuda(values, "values")
-        vd = values.shape[1] if vd is None else vd
-        stride = self.values_stride(vd)
-        assert values.shape[1] == stride and values.is_contiguous()
-        if values.shape[0] < self.m:
-            raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
-        need = int(nv.lib().plx_blur_sym_work_floats(self._h, vd))
-        if need < 0:
-            raise ValueError(f"blur_sym_f32 needs a built lattice and vd >= 1, got vd = {vd}")
-        if work is None:
-            work = torch.empty(need, dtype=torch.float32, device=self.device)
-        elif work.numel() < need or not work.is_contiguous() or work.dtype != torch.float32:
-            raise ValueError(f"work must be a contiguous float32 buffer of at least {need} elements")
-        res = ctypes.c_void_p(0)
-        with torch.cuda.device(self.device):
-            rc = nv.lib().plx_blur_sym(self._h, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(work.data_ptr()), vd,
-                                       ctypes.byref(res), _stream_ptr(self.device))
-        nv.check(rc, "plx_blur_sym")
-        if res.value == values.data_ptr():
-            return values[:self.m]
-        off = (res.value - work.data_ptr()) // 4
-        return work.view(-1)[off:off + self.m * stride].view(self.m, stride)
-
-    def _apply_f32_variant(self, src, out, fn, what, f64_name):
-        self._f32_only(src, "src", what, f64_name)
-        self._f32_only(out, "out", what, f64_name)
-        _check_f32_cuda(src, "src")
-        src = self._src(src, self.n_owned)
-        vd = src.shape[1]
-        if out is None:
-            out = torch.empty((self.n_owned, vd), dtype=torch.float32, device=self.device)
-        else:
-            _check_f32_cuda(out, "out")
-        with torch.cuda.device(self.device):
-            rc = getattr(nv.lib(), fn)(self._h, ctypes.c_void_p(src.data_ptr()), vd, ctypes.c_void_p(out.data_ptr()),
-                                       _stream_ptr(self.device))
-        nv.check(rc, fn)
-        return out
+        return self._blur_sym(torch.float32, "plx_blur_sym", "plx_blur_sym_work_floats", "blur_sym_f32",
+                              lambda t, name: self._f32_only(t, name, "blur_sym_f32", "blur_sym"), values, work, vd)
 
     def apply_t_f32(self, src, out=None):
         """out = K^T src in float32: slice(blur_t_f32(splat(src))) on the workspace of apply() (plx_apply_t)."""
-        return self._apply_f32_variant(src, out, "plx_apply_t", "apply_t_f32", "apply_t")
+        return self._apply_variant(torch.float32, "plx_apply_t", lambda t, name: self._f32_only(t, name, "apply_t_f32", "apply_t"),
+                                   src, out)
 
     def apply_sym_f32(self, src, out=None):
         """out = K_s src in float32 with K_s = (K + K^T) / 2: slice(blur_sym_f32(splat(src))) (plx_apply_sym).  K_s is
         symmetric to rounding; it is not proven positive."""
-        return self._apply_f32_variant(src, out, "plx_apply_sym", "apply_sym_f32", "apply_sym")
+        return self._apply_variant(torch.float32, "plx_apply_sym",
+                                   lambda t, name: self._f32_only(t, name, "apply_sym_f32", "apply_sym"), src, out)
 
     def apply_affine_sym_f32(self, src, scale_shift, out=None, want_dot=False):
         """out = a * K_s src + b * src in float32 (plx_apply_affine_sym): apply_affine() with K_s for K -- the same
