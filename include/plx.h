@@ -508,7 +508,7 @@ int plx_diag_f64(plx_lattice *lat, int64_t row_begin, int64_t row_count, int lat
  *                     out[q][c] = sum over r with vid >= 0 of w_r values[vid_r][c] / (1 + 2^-d),
  *                 in the expression forms and corner order of plx_slice_rows / plx_slice_f64: for a query at a build point
  *                 the bits of that point's row of those calls.  An absent corner is skipped, not multiplied by zero.
- *   plx_last_query_kernels  "locate=...;slice_at=..." of the last such calls.
+ *   plx_last_query_kernels  "locate=...;slice_at=...;dots=...;pullback=..." of the last such calls (the last two: below).
  * Each call is one launch: no workspace, no allocation, no read-back, legal under stream capture.  Refusals, all before
  * the launch, the outputs untouched: a NULL pointer (d_mass excepted), nq < 1, vd < 1, a misaligned buffer, an output
  * that aliases an input (PLX_ERR_INVALID); an unbuilt lattice, a sharded or merged one, a build that replayed
@@ -521,6 +521,32 @@ int plx_slice_at(plx_lattice *lat, const float *d_values, int vd, const int32_t 
 int plx_slice_at_f64(plx_lattice *lat, const double *d_values, int vd, const int32_t *d_vid, const float *d_w, int64_t nq,
                      double *d_out, void *stream);
 int plx_last_query_kernels(const plx_lattice *lat, char *buf, int cap);
+
+/*
+ * The position gradient of a query (callers detect it by symbol; the version string is unchanged).  plx_slice_at is
+ * piecewise linear in the query position: inside the simplex plx_locate chose, the weights are affine in it.  For an
+ * upstream gradient d_gout [nq][vd] of plx_slice_at's output, the exact derivative of what the forward computes is two
+ * launches with the array d_t [d+1][nq] between them, which the caller supplies:
+ *   plx_slice_at_dots / plx_slice_at_dots_f64
+ *                 d_t[r][q] = <d_gout[q][:], d_values[d_vid[r][q]][:]> / (1 + 2^-d) for the corners found, exactly 0 for the
+ *                 absent ones (no gather: the vertex array may be non-finite elsewhere, and in its stride padding).  The
+ *                 derivative with respect to the weight d_w[r][q].  d_values, vd, d_vid as for plx_slice_at.
+ *   plx_locate_pullback / plx_locate_pullback_f64
+ *                 d_gx[q][j] = s_j (sum_{i <= j} e_i - (j + 1) e_{j+1}),  e_i = (t[d - rk_i] - t[(d + 1 - rk_i) mod (d + 1)]) / (d + 1),
+ *                 dense [nq][d], with s the build's scale factors and rk the rank permutation of the embedding, recomputed
+ *                 from the SAME d_x plx_locate read (so the simplex is the one it chose).  A query plx_locate rejects
+ *                 (out of the key range, NaN, Inf) gets a zero row.  d_t need not come from plx_slice_at_dots: any
+ *                 derivative with respect to the weights is pulled back.
+ * No atomics; two calls give the same bits.  Gradients with respect to d_values are not computed.  Each call is one launch
+ * with no workspace, legal under stream capture, and refuses what plx_slice_at / plx_locate refuse, the outputs untouched;
+ * nq * (d + 1) >= 2^31 is PLX_ERR_TOO_LARGE.
+ */
+int plx_slice_at_dots(plx_lattice *lat, const float *d_values, int vd, const int32_t *d_vid, const float *d_gout, int64_t nq,
+                      float *d_t, void *stream);
+int plx_slice_at_dots_f64(plx_lattice *lat, const double *d_values, int vd, const int32_t *d_vid, const double *d_gout,
+                          int64_t nq, double *d_t, void *stream);
+int plx_locate_pullback(plx_lattice *lat, const float *d_x, const float *d_t, int64_t nq, float *d_gx, void *stream);
+int plx_locate_pullback_f64(plx_lattice *lat, const float *d_x, const double *d_t, int64_t nq, double *d_gx, void *stream);
 
 /*
  * The float64 position gradient (callers detect it by symbol; the version string is unchanged): plx_apply_backward with

@@ -1075,10 +1075,93 @@ int plx_slice_at_f64(plx_lattice *L, const double *d_values, int vd, const int32
     return slice_at_impl<double>(L, d_values, vd, d_vid, d_w, nq, d_out, (hipStream_t)stream);
 }
 
+// Everything a slice_at_dots call checks before its one launch: check_slice_at with the upstream gradient in the place of
+// the weights and the [d + 1][nq] dots in the place of the output.
+static int check_slice_at_dots(const plx_lattice *L, const void *d_values, int vd, const void *d_vid, const void *d_gout,
+                               int64_t nq, const void *d_t, size_t esz, int stride, const char *who)
+{
+    if (!L || !d_values || !d_vid || !d_gout || !d_t) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (nq < 1) { set_error("%s: nq = %lld must be positive", who, (long long)nq); return PLX_ERR_INVALID; }
+    if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    if (((uintptr_t)d_vid & 3) != 0 || (((uintptr_t)d_values | (uintptr_t)d_gout | (uintptr_t)d_t) & (esz - 1)) != 0) {
+        set_error("%s: buffers must be aligned to their element size", who);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, who));
+    PLX_TRY(check_query_lattice(L, who));
+    PLX_TRY(check_size(L, stride, nq, "nq", who));
+    const int d1 = L->d + 1;
+    if (nq * d1 >= (1ll << 31)) { set_error("%s: nq*(d+1) exceeds 2^31 elements; split the queries", who); return PLX_ERR_TOO_LARGE; }
+    const size_t nt = (size_t)nq * d1 * esz, ng = (size_t)nq * vd * esz, ne = (size_t)nq * d1 * 4, nv = (size_t)L->m * stride * esz;
+    if (ranges_overlap(d_t, nt, d_values, nv) || ranges_overlap(d_t, nt, d_vid, ne) || ranges_overlap(d_t, nt, d_gout, ng)) {
+        set_error("%s: d_t must not overlap d_values, d_vid or d_gout", who);
+        return PLX_ERR_INVALID;
+    }
+    return PLX_OK;
+}
+
+int plx_slice_at_dots(plx_lattice *L, const float *d_values, int vd, const int32_t *d_vid, const float *d_gout, int64_t nq,
+                      float *d_t, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_slice_at_dots(L, d_values, vd, d_vid, d_gout, nq, d_t, sizeof(float), vd >= 1 ? values_stride(vd) : 1,
+                                "plx_slice_at_dots"));
+    DeviceGuard g(L->device);
+    return slice_at_dots_impl<float>(L, d_values, vd, d_vid, d_gout, nq, d_t, (hipStream_t)stream);
+}
+
+int plx_slice_at_dots_f64(plx_lattice *L, const double *d_values, int vd, const int32_t *d_vid, const double *d_gout, int64_t nq,
+                          double *d_t, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_slice_at_dots(L, d_values, vd, d_vid, d_gout, nq, d_t, sizeof(double), vd >= 1 ? values_stride_f64(vd) : 1,
+                                "plx_slice_at_dots_f64"));
+    DeviceGuard g(L->device);
+    return slice_at_dots_impl<double>(L, d_values, vd, d_vid, d_gout, nq, d_t, (hipStream_t)stream);
+}
+
+// Everything a locate_pullback call checks before its one launch.  `esz`: bytes of an element of d_t and d_gx.
+static int check_locate_pullback(const plx_lattice *L, const void *d_x, const void *d_t, int64_t nq, const void *d_gx, size_t esz,
+                                 const char *who)
+{
+    if (!L || !d_x || !d_t || !d_gx) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (nq < 1) { set_error("%s: nq = %lld must be positive", who, (long long)nq); return PLX_ERR_INVALID; }
+    if (((uintptr_t)d_x & 3) != 0 || (((uintptr_t)d_t | (uintptr_t)d_gx) & (esz - 1)) != 0) {
+        set_error("%s: buffers must be aligned to their element size", who);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_query_lattice(L, who));
+    const int d1 = L->d + 1;
+    if (nq * d1 >= (1ll << 31)) { set_error("%s: nq*(d+1) exceeds 2^31 elements; split the queries", who); return PLX_ERR_TOO_LARGE; }
+    const size_t nx = (size_t)nq * L->d * 4, nt = (size_t)nq * d1 * esz, ng = (size_t)nq * L->d * esz;
+    if (ranges_overlap(d_gx, ng, d_x, nx) || ranges_overlap(d_gx, ng, d_t, nt)) {
+        set_error("%s: d_gx must not overlap d_x or d_t", who);
+        return PLX_ERR_INVALID;
+    }
+    return PLX_OK;
+}
+
+int plx_locate_pullback(plx_lattice *L, const float *d_x, const float *d_t, int64_t nq, float *d_gx, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_locate_pullback(L, d_x, d_t, nq, d_gx, sizeof(float), "plx_locate_pullback"));
+    DeviceGuard g(L->device);
+    return locate_pullback_impl<float>(L, d_x, d_t, nq, d_gx, (hipStream_t)stream);
+}
+
+int plx_locate_pullback_f64(plx_lattice *L, const float *d_x, const double *d_t, int64_t nq, double *d_gx, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_locate_pullback(L, d_x, d_t, nq, d_gx, sizeof(double), "plx_locate_pullback_f64"));
+    DeviceGuard g(L->device);
+    return locate_pullback_impl<double>(L, d_x, d_t, nq, d_gx, (hipStream_t)stream);
+}
+
 int plx_last_query_kernels(const plx_lattice *L, char *buf, int cap)
 {
     if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
-    snprintf(buf, (size_t)cap, "locate=%s;slice_at=%s", L->kn_locate, L->kn_slice_at);
+    snprintf(buf, (size_t)cap, "locate=%s;slice_at=%s;dots=%s;pullback=%s", L->kn_locate, L->kn_slice_at, L->kn_dots,
+             L->kn_pullback);
     return PLX_OK;
 }
 

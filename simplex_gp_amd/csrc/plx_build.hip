@@ -2406,6 +2406,62 @@ static int locate_typed(plx_lattice *L, const float *d_x, int64_t nq, int32_t *d
     return PLX_OK;
 }
 
+// locate pull-back (plx_locate_pullback): the position gradient of a located query from the derivatives t[r][q] of the
+// caller's scalar with respect to the weights w[r][q] (SoA [d + 1][nq]; for a slice, slice_at_dots_* of plx_query_kernels.h).
+// Inside the simplex locate chose the weights are affine in the position, so this is exact for what locate computes:
+//   barycentric  bary[k] = sd[d - k] - sd[d + 1 - k], bary[0] = sd[d] + 1 - sd[0], sd[rk_i] = (el_i - gr_i) / (d + 1):
+//                e_i = (t[d - rk_i] - t[(d + 1 - rk_i) mod (d + 1)]) / (d + 1)
+//   elevate      el_i = sum_{j >= i} s_j p_j - i s_{i-1} p_{i-1}:
+//                gx_j = s_j (sum_{i <= j} e_i - (j + 1) e_{j+1})
+// One query per thread, registers only.  el, gr and rk are recomputed from x by the embedding's own code, so the simplex is
+// the one locate_kernel found, bit for bit; u is indexed by rank with selects, as barycentric() indexes sd.  T is the type
+// of t and gx (the fp32 scale factors convert exactly).  A query nearest_vertex rejects gets a zero row.
+template <int D, typename T>
+__global__ __launch_bounds__(kBlock) void locate_pullback_kernel(const float *__restrict__ x, int64_t nq, ScaleArgs sf,
+                                                                 const T *__restrict__ t, T *__restrict__ gx)
+{
+    constexpr int D1 = D + 1;
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= nq) return;
+    float pos[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) pos[i] = x[(size_t)q * D + i];
+    float el[D1];
+    elevate<D>(pos, sf, el);
+    int gr[D1], rk[D1];
+    const bool bad = nearest_vertex<D>(el, gr, rk);
+    T tr[D1], u[D1];    // u[k]: the derivative with respect to sd[k]
+#pragma unroll
+    for (int r = 0; r < D1; ++r) tr[r] = t[(size_t)r * nq + q];
+    u[0] = tr[D] - tr[0];
+#pragma unroll
+    for (int k = 1; k < D1; ++k) u[k] = tr[D - k] - tr[D1 - k];
+    T e[D1];
+#pragma unroll
+    for (int i = 0; i < D1; ++i) {
+        T ui = (T)0;
+#pragma unroll
+        for (int k = 0; k < D1; ++k) ui = (rk[i] == k) ? u[k] : ui;
+        e[i] = ui / (T)D1;
+    }
+    T run = (T)0;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        run += e[j];
+        const T v = (T)sf.v[j] * (run - (T)(j + 1) * e[j + 1]);
+        gx[(size_t)q * D + j] = bad ? (T)0 : v;
+    }
+}
+
+template <int D, typename T>
+static int locate_pullback_typed(plx_lattice *L, const float *d_x, const T *d_t, int64_t nq, T *d_gx, hipStream_t stream)
+{
+    locate_pullback_kernel<D, T><<<ceil_div(nq, kBlock), kBlock, 0, stream>>>(d_x, nq, scale_args<D>(L), d_t, d_gx);
+    PLX_HIP_TRY(hipGetLastError());
+    L->kn_pullback = "locate_pullback_kernel";
+    return PLX_OK;
+}
+
 #define PLX_DIM_SWITCH(CALL)                                                                                  \
     switch (L->d) {                                                                                           \
         PLX_CASE(1) PLX_CASE(2) PLX_CASE(3) PLX_CASE(4) PLX_CASE(5) PLX_CASE(6) PLX_CASE(7) PLX_CASE(8)       \
@@ -2430,6 +2486,16 @@ int locate_impl(plx_lattice *L, const float *d_x, int64_t nq, int32_t *d_vid, fl
     PLX_DIM_SWITCH()
 #undef PLX_CASE
 }
+
+template <typename T>
+int locate_pullback_impl(plx_lattice *L, const float *d_x, const T *d_t, int64_t nq, T *d_gx, hipStream_t stream)
+{
+#define PLX_CASE(D) case D: return locate_pullback_typed<D, T>(L, d_x, d_t, nq, d_gx, stream);
+    PLX_DIM_SWITCH()
+#undef PLX_CASE
+}
+template int locate_pullback_impl<float>(plx_lattice *, const float *, const float *, int64_t, float *, hipStream_t);
+template int locate_pullback_impl<double>(plx_lattice *, const float *, const double *, int64_t, double *, hipStream_t);
 
 int build_local_impl(plx_lattice *L, const float *d_ref, hipStream_t stream)
 {

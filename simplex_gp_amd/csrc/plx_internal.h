@@ -317,6 +317,7 @@ struct plx_lattice {
 
     // queries at points that are not the build's (plx_locate in plx_build.hip, plx_slice_at in plx_query_kernels.h)
     const char *kn_locate = "", *kn_slice_at = "";   // kernels of the last query calls (plx_last_query_kernels)
+    const char *kn_dots = "", *kn_pullback = "";     // ... and of the last plx_slice_at_dots* / plx_locate_pullback*
 };
 
 namespace plx {
@@ -331,6 +332,11 @@ int build_impl(plx_lattice *L, const float *d_ref, hipStream_t stream);
 int build_local_impl(plx_lattice *L, const float *d_ref, hipStream_t stream);
 // plx_locate: the corners of nq foreign points in the current build's numbering (arguments checked by the entry point)
 int locate_impl(plx_lattice *L, const float *d_x, int64_t nq, int32_t *d_vid, float *d_w, float *d_mass, hipStream_t stream);
+// plx_locate_pullback / plx_locate_pullback_f64: d_gx[q][0..d) = the position gradient of query q from d_t[r][q], the
+// derivative with respect to its r-th weight (locate_pullback_kernel, plx_build.hip; T = float or double, instantiated
+// there; arguments checked by the entry points).  One launch, no workspace.
+template <typename T>
+int locate_pullback_impl(plx_lattice *L, const float *d_x, const T *d_t, int64_t nq, T *d_gx, hipStream_t stream);
 int build_merge_impl(plx_lattice *L, const uint32_t *d_all_keys, const int64_t *h_counts, int n_ranks, int my_rank,
                      hipStream_t stream);
 int read_back(plx_lattice *L, const int *d_src, int count, int *h_dst, hipStream_t stream);   // a few device ints to the host, no stream synchronisation
@@ -510,6 +516,11 @@ int diag_impl(plx_lattice *L, int64_t row_begin, int64_t row_count, bool lattice
 template <typename T>
 int slice_at_impl(plx_lattice *L, const T *d_values, int vd, const int32_t *d_vid, const float *d_w, int64_t nq, T *d_out,
                   hipStream_t stream);
+// ... and d_t[r][q] = <d_gout[q], values[vid[r][q]]> / (1 + 2^-d), exactly 0 at absent corners: the corner dots of the
+// position gradient (slice_at_dots_* kernels).  One launch; no workspace.
+template <typename T>
+int slice_at_dots_impl(plx_lattice *L, const T *d_values, int vd, const int32_t *d_vid, const T *d_gout, int64_t nq, T *d_t,
+                       hipStream_t stream);
 
 // contiguous near-equal row blocks: the first n % shards blocks get one extra row
 inline void shard_range(int64_t n, int shards, int index, int64_t *lo, int64_t *hi)

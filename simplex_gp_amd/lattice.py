@@ -52,11 +52,15 @@ class LatticeQuery:
     """Where nq points that are not the build's sit in a built lattice (Lattice.locate): vid [d+1, nq] int32, the vertex id
     of every simplex corner in the numbering of build `build_id` of that lattice, -1 where the corner is not one of its
     vertices; weight [d+1, nq] float32, the barycentric weights; mass [nq] float32 (None when not asked for), the sum of
-    the weights of the corners found: 1 where the whole simplex exists, 0 where the lattice knows nothing of the point."""
-    __slots__ = ("vid", "weight", "mass", "nq", "build_id")
+    the weights of the corners found: 1 where the whole simplex exists, 0 where the lattice knows nothing of the point;
+    x [nq, d] float32 (None when built by hand without it), the contiguous positions locate read -- what the position
+    gradient (simplex_gp_amd.query_grad) recomputes the simplex from.  x is NOT a copy: where the caller's tensor was
+    contiguous float32 already it is that tensor, and changing it in place after locate makes the pull-back recompute
+    another simplex than the one vid and weight describe.  Clone before locate if the positions are to be overwritten."""
+    __slots__ = ("vid", "weight", "mass", "nq", "build_id", "x")
 
-    def __init__(self, vid, weight, mass, nq, build_id):
-        self.vid, self.weight, self.mass, self.nq, self.build_id = vid, weight, mass, int(nq), int(build_id)
+    def __init__(self, vid, weight, mass, nq, build_id, x=None):
+        self.vid, self.weight, self.mass, self.nq, self.build_id, self.x = vid, weight, mass, int(nq), int(build_id), x
 
 
 class Lattice:
@@ -663,20 +667,18 @@ class Lattice:
                                      ctypes.c_void_p(weight.data_ptr()),
                                      ctypes.c_void_p(mass.data_ptr()) if want_mass else None, _stream_ptr(self.device))
         nv.check(rc, "plx_locate")
-        return LatticeQuery(vid, weight, mass, nq, self.build_id)
+        return LatticeQuery(vid, weight, mass, nq, self.build_id, x)
 
-    def slice_at(self, values, query, out=None, vd=None):
-        """out[nq, vd] = S* values / (1 + 2^-d) at the located `query`, in the dtype of `values` (a vertex array
-        [>= m, values_stride(vd, dtype)], e.g. what blurred() returns).  A query located before the lattice's last build is
-        refused: its vertex ids belong to another numbering."""
+    def _check_sliced(self, who, values, query, vd, symbols):
+        """What slice_at and the calls of its position gradient check about (values, query, vd) before any device work:
+        (f64, vd).  symbols: the library calls `who` needs, (for float32 values, for float64 values)."""
         if not isinstance(query, LatticeQuery):
             raise TypeError(f"query must be a LatticeQuery (Lattice.locate), got {type(query).__name__}")
         _check_f32_cuda(values, "values", f64_ok=True)
         f64 = values.dtype == torch.float64
-        fn = "plx_slice_at_f64" if f64 else "plx_slice_at"
-        self._need_query_symbols("slice_at", fn)
+        self._need_query_symbols(who, *symbols[1 if f64 else 0])
         if query.build_id != self.build_id:
-            raise RuntimeError(f"slice_at: the lattice was rebuilt since this query was located (build {query.build_id}, now "
+            raise RuntimeError(f"{who}: the lattice was rebuilt since this query was located (build {query.build_id}, now "
                                f"{self.build_id}): locate the points again")
         vd = values.shape[1] if vd is None else int(vd)
         if vd < 1 or values.shape[1] != self.values_stride(vd, values.dtype) or not values.is_contiguous():
@@ -686,6 +688,14 @@ class Lattice:
             raise ValueError(f"values has {values.shape[0]} rows, the lattice {self.m} vertices")
         if values.device != self.device or query.vid.device != self.device:
             raise ValueError(f"values and query must be on {self.device}")
+        return f64, vd
+
+    def slice_at(self, values, query, out=None, vd=None):
+        """out[nq, vd] = S* values / (1 + 2^-d) at the located `query`, in the dtype of `values` (a vertex array
+        [>= m, values_stride(vd, dtype)], e.g. what blurred() returns).  A query located before the lattice's last build is
+        refused: its vertex ids belong to another numbering."""
+        f64, vd = self._check_sliced("slice_at", values, query, vd, (("plx_slice_at",), ("plx_slice_at_f64",)))
+        fn = "plx_slice_at_f64" if f64 else "plx_slice_at"
         if out is None:
             out = torch.empty((query.nq, vd), dtype=values.dtype, device=self.device)
         elif not isinstance(out, torch.Tensor) or out.dtype != values.dtype:
@@ -713,7 +723,8 @@ class Lattice:
     def query_kernels(self):
         """Kernels launched by the last locate / slice_at on this lattice: {"locate": [...], "slice_at": [...]}."""
         self._need_query_symbols("query_kernels", "plx_last_query_kernels")
-        return self._last_kernels("plx_last_query_kernels", 256)
+        names = self._last_kernels("plx_last_query_kernels", 256)
+        return {k: names[k] for k in ("locate", "slice_at")}
 
     # -- the rectangular product: splat / slice by row range (plx_*_rows) ------
     def _rows(self, begin, count):

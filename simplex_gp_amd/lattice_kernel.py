@@ -17,6 +17,7 @@ from collections import OrderedDict
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from .gp_compat import Kernel, LazyTensor
 from .lattice import Lattice, _taps_array
@@ -393,6 +394,40 @@ class LatticeRowsProduct(Function):
                 lat = _cache.get(ctx.positions, ctx.coeffs)       # the forward's lattice (rebuilt if it was evicted since)
                 grad_source = lat.apply_rows(grad_output.contiguous(), ob, sb, sc)
         return grad_source, grad_positions, None, None, None, None, None, None
+
+
+class LatticeSliceAt(Function):
+    """(out, mass) = the vertex array `values` of the built lattice `lat` sliced at the points x [nq, d] (in the build's
+    units: already divided by the lengthscale): Lattice.locate + Lattice.slice_at, differentiable in x.
+
+    The slice is piecewise linear in x; the backward is its exact derivative inside the simplex locate chose
+    (query_grad.slice_at_backward: plx_slice_at_dots + plx_locate_pullback), returned in the dtype of
+    x.  Once differentiable.  `mass` (locate's) carries no gradient.  `values` is a constant: its gradient is the adjoint
+    splat at the query points, which is not built, so a `values` that requires a gradient is refused.  x and values are
+    saved for the backward: changing either in place in between is an autograd error, not a wrong gradient."""
+
+    @staticmethod
+    def forward(ctx, x, values, lat, vd=None):
+        if values.requires_grad:
+            raise RuntimeError("LatticeSliceAt: values requires a gradient, but the adjoint splat at query points is not "
+                               "built; detach values (only the query positions are differentiated)")
+        query = lat.locate(x.detach())
+        out = lat.slice_at(values, query, vd=vd)
+        ctx.lat, ctx.query, ctx.vd = lat, query, vd
+        ctx.save_for_backward(x, values)
+        ctx.mark_non_differentiable(query.mass)
+        return out, query.mass
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_mass):
+        from . import query_grad
+        x, values = ctx.saved_tensors
+        grad_x = None
+        if ctx.needs_input_grad[0]:
+            g = grad_out.to(values.dtype).contiguous()
+            grad_x = query_grad.slice_at_backward(ctx.lat, values, ctx.query, g, vd=ctx.vd).to(x.dtype)
+        return grad_x, None, None, None
 
 
 def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1, f64=False,

@@ -316,6 +316,33 @@ class PredictionCache:
         prior = s * model.kernel(x_star, x_star, diag=True)
         return mean, (prior - (proj ** 2).sum(0)).clamp_min(1e-8)
 
+    def predict_query_grad(self, x_star):
+        """route="query" of predict(), differentiable in x_star: (mean, variance) attached to a graph through
+        lattice_kernel.LatticeSliceAt, whose backward is the exact derivative of the piecewise-linear slice inside the
+        simplex of every test point (two launches: corner dots, pull-back through the embedding).  Only x_star is
+        differentiated: the blurred [alpha, Q] values, the lengthscale, the output scale and the mean are constants of the
+        cache (they were computed without a graph; the lengthscale's gradient runs through `values` and is not built).
+        Query route only: raises where predict(route="query") would fall through to the stacked route.  The variance's clamp
+        at 1e-8 passes no gradient where it is active."""
+        with torch.no_grad():
+            st = self._query_state()
+        if st is None:
+            raise RuntimeError("predict_query_grad: the query route is not served here (it needs the HIP path, CUDA float32 or "
+                               "float64 training points and a plain lattice build); the stacked route has no query gradient")
+        from . import lattice_kernel as lk
+        model = self.model
+        lat, values, vd, _ = st
+        s, mu = model.outputscale.detach(), model.mean.detach()
+        out, mass = lk.LatticeSliceAt.apply(x_star.div(model.kernel.lengthscale.detach()), values, lat, vd)
+        self.last_query_mass = mass
+        KAQ = s * out                                                                       # [n*, 1 + t]
+        mean = mu + KAQ[:, 0]
+        if self.Q is None:
+            return mean, None
+        proj = torch.linalg.solve_triangular(self.chol, KAQ[:, 1:].t(), upper=False)
+        prior = s * model.kernel(x_star, x_star, diag=True).detach()
+        return mean, (prior - (proj ** 2).sum(0)).clamp_min(1e-8)
+
 
 @torch.no_grad()
 def predict(model, x, y, x_star, max_cg_iter=1000, cg_tol=1e-2, lanc_iter=100, variance=True, pre_size=100, cache=None,
