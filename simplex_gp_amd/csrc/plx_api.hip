@@ -456,7 +456,7 @@ int plx_apply_affine_dot(plx_lattice *L, const float *d_src, int vd, float *d_ou
     PLX_TRY(blur_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), vd, &in_b, s));
     PLX_TRY(slice_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, d_out, s, d_scale_shift, d_src, d_work));
     if (!d_dot) return PLX_OK;          // the per-tile partial sums stay in d_work (plx_cg_step_update_fused adds them up itself)
-    return coldot_final(d_work, affine_dot_tiles(L, vd), vdp, d_dot, s);
+    return coldot_final(d_work, affine_dot_tiles(L, vd), vdp, vdp, d_dot, s);
 }
 
 int plx_affine_dot_tiles(const plx_lattice *L, int vd)
@@ -664,7 +664,7 @@ int plx_apply_affine_f64(plx_lattice *L, const double *d_src, int vd, double *d_
     PLX_TRY(slice_affine_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, d_src, d_scale_shift, d_out,
                                   d_dot ? d_work : nullptr, s));
     if (!d_dot) return PLX_OK;
-    return coldot_final_f64(d_work, dot_rows, values_stride_f64(vd), vd, d_dot, s);
+    return coldot_final(d_work, dot_rows, values_stride_f64(vd), vd, d_dot, s);
 }
 
 int plx_last_f64_kernels(const plx_lattice *L, char *buf, int cap)
@@ -887,7 +887,7 @@ int plx_apply_affine_sym_f64(plx_lattice *L, const double *d_src, int vd, double
     PLX_TRY(splat_blur_sym<double>(L, d_src, vd, &blurred, s));
     PLX_TRY(slice_affine_f64_impl(L, blurred, vd, d_src, d_scale_shift, d_out, d_dot ? d_work : nullptr, s));
     if (!d_dot) return PLX_OK;
-    return coldot_final_f64(d_work, dot_rows, values_stride_f64(vd), vd, d_dot, s);
+    return coldot_final(d_work, dot_rows, values_stride_f64(vd), vd, d_dot, s);
 }
 
 int plx_last_sym_f64_kernels(const plx_lattice *L, char *buf, int cap)
@@ -943,7 +943,7 @@ int plx_apply_affine_sym(plx_lattice *L, const float *d_src, int vd, float *d_ou
     PLX_TRY(splat_blur_sym<float>(L, d_src, vd, &blurred, s));
     PLX_TRY(slice_impl(L, blurred, vd, d_out, s, d_scale_shift, d_src, d_work));
     if (!d_dot) return PLX_OK;          // d_work set: the per-tile partial sums stay there (plx_cg_step_update_fused adds them up)
-    return coldot_final(d_work, affine_dot_tiles(L, vd), values_stride(vd), d_dot, s);
+    return coldot_final(d_work, affine_dot_tiles(L, vd), values_stride(vd), values_stride(vd), d_dot, s);
 }
 
 int plx_last_sym_kernels(const plx_lattice *L, char *buf, int cap)

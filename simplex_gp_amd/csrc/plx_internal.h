@@ -429,18 +429,31 @@ int blur_sym_f64_planes(const plx_lattice *L);
 int blur_sym_f64_impl(plx_lattice *L, double *d_values, double *const d_work[3], int vd, double **d_result, hipStream_t stream);
 // plx_cg_f64.hip: the fp64 slice with the affine tail out = a y + b src fused (and, unless d_partial is NULL, one partial
 // row of <src, out> per workgroup: affine_f64_dot_rows rows of values_stride_f64(vd) doubles; 0 rows: the shape serves no
-// dot), and the final stage of plx_coldot_f64: out[c] = sum over nrows of partial[k * stride + c], c < vd, fixed order
+// dot)
 int affine_f64_dot_rows(const plx_lattice *L, int vd);
 int slice_affine_f64_impl(plx_lattice *L, const double *d_values, int vd, const double *d_src, const double *d_ss,
                           double *d_out, double *d_partial, hipStream_t stream);
-int coldot_final_f64(const double *d_partial, int nrows, int stride, int vd, double *d_out, hipStream_t stream);
-// plx_cg_f64.hip, shared with plx_pcg_f64.hip: what every float64 vector call checks before any launch (ptrs: every pointer
-// argument: non-NULL, 8-byte aligned; 1 <= vd <= kBlock, n >= 1; `who` prefixes the error text), and the direction step of
-// plx_cg_step_direction_f64 (src = R, num = rr = |R'|^2, den = |R|^2) and plx_pcg_step_direction_f64, arguments checked
-int check_cg64(const char *who, std::initializer_list<const void *> ptrs, int64_t n, int vd);
-int step_direction_f64(const char *who, double *d_p, const double *d_src, const double *d_num, const double *d_den,
-                       const double *d_rr, const double *d_active, const double *d_b_norm, double tol, int64_t n, int vd,
-                       double *d_beta, double *d_active_out, hipStream_t stream);
+// plx_cg_kernels.h with T = float (plx_linalg.hip) and T = double (plx_cg_f64.hip).
+// What an entry point of the CG vector steps accepts, checked by cg_check before any launch, in this order: every pointer
+// of ptrs non-NULL; [alias_first: not aliased;] 1 <= vd <= kBlock (and n >= 0, under the same text); n >= min_n; every
+// pointer a multiple of `align` bytes; not aliased (the direction steps: active == active_out).
+struct CgRules {
+    const char *who;        // prefixes the error text
+    int64_t min_n;          // fp32: 0, float64: 1
+    int align;              // fp32: 1 (no rule), float64: 8
+    bool alias_first;       // fp32: true
+};
+constexpr CgRules cg_rules_f32(const char *who) { return {who, 0, 1, true}; }
+constexpr CgRules cg_rules_f64(const char *who) { return {who, 1, 8, false}; }
+int cg_check(const CgRules &rules, std::initializer_list<const void *> ptrs, int64_t n, int vd, bool aliased = false);
+// the final stage of a column dot: out[c] = sum over nrows of partial[k * stride + c], c < vd, fixed order
+template <class T> int coldot_final(const T *d_partial, int nrows, int stride, int vd, T *d_out, hipStream_t stream);
+// the direction step of plx_cg_step_direction[_f64] (src = R, num = rr = |R'|^2, den = |R|^2) and of
+// plx_pcg_step_direction[_f64] (src = Z, num = <R', Z'>, den = <R, Z>, rr = the true |R'|^2), arguments checked
+template <class T>
+int cg_step_direction(const CgRules &rules, T *d_p, const T *d_src, const T *d_num, const T *d_den, const T *d_rr,
+                      const T *d_active, const T *d_b_norm, T tol, int64_t n, int vd, T *d_beta, T *d_active_out,
+                      hipStream_t stream);
 // plx_backward_f64.hip: the float64 position gradient on the derivative-tap lattice -- the splat that forms the stacked
 // matrix [ g | g (x) x | src | src (x) x ] (2 nrhs (1 + d) columns) on the fly, and the slice with the contraction fused
 // (arguments checked by the entry points).  kBackwardF64MaxCols: the widest stack the on-chip row of the contraction holds.
@@ -449,8 +462,6 @@ int backward_splat_f64_impl(plx_lattice *L, const double *d_g, const double *d_s
                             double *d_values, hipStream_t stream);
 int backward_contract_f64_impl(plx_lattice *L, const double *d_values, const double *d_g, const double *d_src,
                                const double *d_x, int nrhs, double *d_grad_x, double *d_grad_src, hipStream_t stream);
-// plx_linalg.hip: out[c] = sum over nblocks of partial[k * vd + c], fixed order
-int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream);
 int backward_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_grad_x,
                   float *d_grad_src, hipStream_t stream);
 int splat_stack_impl(plx_lattice *L, const float *d_g, const float *d_src, const float *d_x, int nrhs, float *d_values,

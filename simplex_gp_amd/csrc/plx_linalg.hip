@@ -1,215 +1,37 @@
-// plx_linalg.hip -- the one dense reduction the CG caller needs next to the MVM:
-// column-wise dot products of two row-major [n][vd] matrices (vd = 1 + probes is
-// small, n is large), deterministic.  torch's (a*b).sum(0) takes 1.3 ms on
-// [1e6][11]; this is two streaming reads (~20 us).
-#include "plx_internal.h"
+// plx_linalg.hip -- the fp32 dense vector work around the MVM (include/plx.h):
+//   the CG vector steps plx_coldot, plx_cg_update, plx_cg_step_update, plx_cg_step_direction: plx_cg_kernels.h with
+//       T = float -- this file holds the fp32 kernels, the entry points, and the two launchers plx_pcg.hip and plx_api.hip
+//       call (the final column sum, the direction step) -- and cg_check, what every vector call of either type checks;
+//   the fused forms of the update and the direction step, which sum the partial rows of the dots themselves (fp32 only);
+//   plx_cg_direction, the direction step with beta given;
+//   the two elementwise ends of the position gradient, plx_backward_stack and plx_backward_contract.
+#include "plx_cg_kernels.h"
 
 #include <algorithm>
 
 namespace plx {
 
-constexpr int kDotBlocks = 1024;
+PLX_CG_INSTANTIATE(float)
 
-// threads = (row lane, column lane), column fastest, vd lanes per row: a workgroup step covers kBlock / vd whole rows,
-// i.e. consecutive threads read consecutive floats (with a power-of-two lane count per row, 5 of 16 lanes idled at
-// vd = 11 and every row was its own 44-byte segment: cg_step_update 51-55 -> 49 us, 46 us being its streaming floor)
-__global__ __launch_bounds__(kBlock) void coldot_partial_kernel(const float *__restrict__ a,
-                                                                const float *__restrict__ b, int64_t n, int vd,
-                                                                int cw, float *__restrict__ partial)
+int cg_check(const CgRules &rules, std::initializer_list<const void *> ptrs, int64_t n, int vd, bool aliased)
 {
-    __shared__ float red[kBlock];
-    const int c = threadIdx.x % cw;
-    const int rl = threadIdx.x / cw;
-    const int rows_per_step = kBlock / cw;
-    const int64_t rows_per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = min(r0 + rows_per_block, n);
-    float acc = 0.f;
-    if (rl < rows_per_step)
-        for (int64_t r = r0 + rl; r < r1; r += rows_per_step) acc += a[r * vd + c] * b[r * vd + c];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    // fixed-order sum over the row lanes of each column
-    if (rl == 0 && c < vd) {
-        float s = 0.f;
-        for (int k = 0; k < rows_per_step; ++k) s += red[k * cw + c];
-        partial[(size_t)blockIdx.x * vd + c] = s;
+    const char *who = rules.who;
+    uintptr_t bits = 0;
+    for (const void *q : ptrs) {
+        if (!q) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+        bits |= (uintptr_t)q;
     }
-}
-
-// One workgroup per column; 1024 threads with four independent loads in flight each (the partials of the fused
-// slice + dot are one row per 256-thread tile: 11,719 rows at N = 1e6, vd = 12 -- 256 threads with one load in flight
-// took 11 us, twice per CG iteration).  Fixed summation order: thread-strided partial sums, then a tree.
-constexpr int kFinalBlock = 1024;
-__global__ __launch_bounds__(kFinalBlock) void coldot_final_kernel(const float *__restrict__ partial, int nblocks, int vd,
-                                                                   float *__restrict__ out)
-{
-    __shared__ float red[kFinalBlock];
-    const int c = blockIdx.x;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int k = threadIdx.x;
-    for (; k + 3 * kFinalBlock < nblocks; k += 4 * kFinalBlock) {
-        const float p0 = partial[(size_t)k * vd + c], p1 = partial[(size_t)(k + kFinalBlock) * vd + c];
-        const float p2 = partial[(size_t)(k + 2 * kFinalBlock) * vd + c], p3 = partial[(size_t)(k + 3 * kFinalBlock) * vd + c];
-        a0 += p0; a1 += p1; a2 += p2; a3 += p3;
-    }
-    for (; k < nblocks; k += kFinalBlock) a0 += partial[(size_t)k * vd + c];
-    red[threadIdx.x] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    for (int s = kFinalBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[c] = red[0];
-}
-
-// CG vector updates fused into one pass each (the torch formulation is 2 addcmul_ + a column dot = three
-// passes over [n][vd] plus a mul_/add_ pair for the direction).
-//   update:    X += P * alpha;  R -= AP * alpha;  partial[c] += R[.][c]^2      (alpha per column)
-//   direction: P  = R + P * beta                                                 (beta per column)
-__global__ __launch_bounds__(kBlock) void cg_update_kernel(float *__restrict__ X, float *__restrict__ R,
-                                                           const float *__restrict__ P, const float *__restrict__ AP,
-                                                           const float *__restrict__ alpha, int64_t n, int vd,
-                                                           int cw, float *__restrict__ partial)
-{
-    __shared__ float red[kBlock];
-    const int c = threadIdx.x % cw;
-    const int rl = threadIdx.x / cw;
-    const int rows_per_step = kBlock / cw;
-    const int64_t rows_per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = min(r0 + rows_per_block, n);
-    float acc = 0.f;
-    if (rl < rows_per_step) {                            // (the last kBlock % vd threads have no row lane)
-        const float a = alpha[c];
-        for (int64_t r = r0 + rl; r < r1; r += rows_per_step) {
-            const int64_t i = r * vd + c;
-            X[i] += P[i] * a;
-            const float res = R[i] - AP[i] * a;
-            R[i] = res;
-            acc += res * res;
-        }
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (rl == 0 && c < vd) {
-        float s = 0.f;
-        for (int k = 0; k < rows_per_step; ++k) s += red[k * cw + c];
-        partial[(size_t)blockIdx.x * vd + c] = s;
-    }
-}
-
-// The same two updates with the CG coefficients formed on the device from the iteration's
-// scalars (no host round trip, none of the ten tiny elementwise launches a tensor-library
-// formulation of "alpha = active ? rs / pAp : 0" costs per iteration):
-//   step_update:     alpha = active ? rs / max(pAp, tiny) : 0;  X += alpha P;  R -= alpha AP;  partial |R|^2
-//   step_direction:  beta = active ? rs_new / max(rs, tiny) : 0;  P = R + beta P;
-//                    active' = active and sqrt(rs_new) / b_norm > tol
-__global__ __launch_bounds__(kBlock) void cg_step_update_kernel(float *__restrict__ X, float *__restrict__ R,
-                                                                const float *__restrict__ P, const float *__restrict__ AP,
-                                                                const float *__restrict__ rs, const float *__restrict__ pAp,
-                                                                const float *__restrict__ active, int64_t n, int vd,
-                                                                int cw, float *__restrict__ partial,
-                                                                float *__restrict__ alpha_out)
-{
-    __shared__ float red[kBlock];
-    const int c = threadIdx.x % cw;
-    const int rl = threadIdx.x / cw;
-    const int rows_per_step = kBlock / cw;
-    const int64_t rows_per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = min(r0 + rows_per_block, n);
-    float acc = 0.f;
-    if (rl < rows_per_step) {                            // (the last kBlock % vd threads have no row lane)
-        const float a = active[c] > 0.f ? rs[c] / fmaxf(pAp[c], 1e-30f) : 0.f;
-        if (blockIdx.x == 0 && rl == 0) alpha_out[c] = a;
-        for (int64_t r = r0 + rl; r < r1; r += rows_per_step) {
-            const int64_t i = r * vd + c;
-            X[i] += P[i] * a;
-            const float res = R[i] - AP[i] * a;
-            R[i] = res;
-            acc += res * res;
-        }
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (rl == 0 && c < vd) {
-        float s = 0.f;
-        for (int k = 0; k < rows_per_step; ++k) s += red[k * cw + c];
-        partial[(size_t)blockIdx.x * vd + c] = s;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void cg_step_direction_kernel(float *__restrict__ P, const float *__restrict__ R,
-                                                                   const float *__restrict__ rs_new,
-                                                                   const float *__restrict__ rs,
-                                                                   const float *__restrict__ active,
-                                                                   const float *__restrict__ b_norm, float tol,
-                                                                   int64_t total, int vd, float *__restrict__ beta_out,
-                                                                   float *__restrict__ active_out)
-{
-    // beta per column once per workgroup; the column of element i = blockIdx * kBlock + tid from 32-bit
-    // residues (a 64-bit i % vd per element costs more than the update itself)
-    __shared__ float sbeta[kBlock];
-    if ((int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        sbeta[c] = active[c] > 0.f ? rs_new[c] / fmaxf(rs[c], 1e-30f) : 0.f;
-    }
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < total) {
-        const uint32_t uvd = (uint32_t)vd;
-        const uint32_t bm = ((blockIdx.x % uvd) * ((uint32_t)kBlock % uvd)) % uvd;      // wave-uniform
-        const uint32_t c = (bm + threadIdx.x) % uvd;
-        P[i] = R[i] + P[i] * sbeta[c];
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        const bool on = active[c] > 0.f;
-        beta_out[c] = on ? rs_new[c] / fmaxf(rs[c], 1e-30f) : 0.f;
-        active_out[c] = (on && sqrtf(rs_new[c]) / b_norm[c] > tol) ? 1.f : 0.f;
-    }
-}
-
-// the same four elements per thread (16-byte loads / stores; total a multiple of 4, P and R 16-byte aligned)
-__global__ __launch_bounds__(kBlock) void cg_step_direction4_kernel(float4 *__restrict__ P, const float4 *__restrict__ R,
-                                                                    const float *__restrict__ rs_new,
-                                                                    const float *__restrict__ rs,
-                                                                    const float *__restrict__ active,
-                                                                    const float *__restrict__ b_norm, float tol,
-                                                                    int64_t quads, int vd, float *__restrict__ beta_out,
-                                                                    float *__restrict__ active_out)
-{
-    __shared__ float sbeta[kBlock];
-    if ((int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        sbeta[c] = active[c] > 0.f ? rs_new[c] / fmaxf(rs[c], 1e-30f) : 0.f;
-    }
-    __syncthreads();
-    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q < quads) {
-        const uint32_t uvd = (uint32_t)vd;
-        // column of element 4 q = 4 (blockIdx kBlock + tid) mod vd, from 32-bit residues
-        const uint32_t bm = ((blockIdx.x % uvd) * ((4u * (uint32_t)kBlock) % uvd)) % uvd;      // wave-uniform
-        uint32_t c = (bm + 4u * threadIdx.x) % uvd;
-        const float4 r = R[q];
-        float4 p = P[q];
-        p.x = r.x + p.x * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
-        p.y = r.y + p.y * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
-        p.z = r.z + p.z * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
-        p.w = r.w + p.w * sbeta[c];
-        P[q] = p;
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        const bool on = active[c] > 0.f;
-        beta_out[c] = on ? rs_new[c] / fmaxf(rs[c], 1e-30f) : 0.f;
-        active_out[c] = (on && sqrtf(rs_new[c]) / b_norm[c] > tol) ? 1.f : 0.f;
-    }
+    if (aliased && rules.alias_first) { set_error("%s: active and active_out must be different buffers", who); return PLX_ERR_INVALID; }
+    // (the fp32 calls have always refused a negative n under the vd text)
+    if (vd < 1 || vd > kBlock || (rules.min_n == 0 && n < 0)) { set_error("%s: vd = %d outside 1..%d", who, vd, kBlock); return PLX_ERR_INVALID; }
+    if (n < rules.min_n) { set_error("%s: n = %lld must be positive", who, (long long)n); return PLX_ERR_INVALID; }
+    if ((bits & (uintptr_t)(rules.align - 1)) != 0) { set_error("%s: buffers of doubles must be %d-byte aligned", who, rules.align); return PLX_ERR_INVALID; }
+    if (aliased) { set_error("%s: active and active_out must be different buffers", who); return PLX_ERR_INVALID; }
+    return PLX_OK;
 }
 
 // ----------------------------------------------------------------------------
-// The same two steps WITHOUT the two stand-alone reductions between them (round 6: a CG iteration was MVM + coldot_final
+// The update and the direction step WITHOUT the two stand-alone reductions between them (round 6: a CG iteration was MVM + coldot_final
 // + update + coldot_final + direction; each coldot_final is a 7 us kernel behind a dependent-launch boundary of about
 // 5 us).  Rows of whole 16-byte chunks (vd = 4 NCH, NCH <= 4: the padded widths solvers.khat_solve runs at).
 //   update_fused:    every workgroup first sums the slice kernel's per-tile partial sums of <P, AP> itself (ntiles rows
@@ -291,7 +113,7 @@ __global__ __launch_bounds__(kFusedThreads) void cg_step_update_fused_kernel(flo
     block_column_sums<NCH, T, 12>(pap_partial, ntiles, wsum, pap);
     if ((int)threadIdx.x < vd) {
         const int c = threadIdx.x;
-        const float a = active[c] > 0.f ? rs[c] / fmaxf(pap[c], 1e-30f) : 0.f;
+        const float a = cg_coef(rs, pap, active, c);
         salpha[c] = a;
         if (blockIdx.x == 0) alpha_out[c] = a;
     }
@@ -338,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_direction_fused_kernel(float4 
     if ((int)threadIdx.x < vd) {
         const int c = threadIdx.x;
         const bool on = active[c] > 0.f;
-        const float b = on ? rsn[c] / fmaxf(rs[c], 1e-30f) : 0.f;
+        const float b = on ? rsn[c] / Cg<float>::guard(rs[c]) : 0.f;
         reinterpret_cast<float *>(sbeta)[c] = b;
         if (blockIdx.x == 0) {
             rs_new_out[c] = rsn[c];
@@ -379,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void pcg_step_direction_fused_kernel(float4
     if ((int)threadIdx.x < vd) {
         const int c = threadIdx.x;
         const bool on = active[c] > 0.f;
-        const float b = on ? rzn[c] / fmaxf(rz[c], 1e-30f) : 0.f;
+        const float b = on ? rzn[c] / Cg<float>::guard(rz[c]) : 0.f;
         reinterpret_cast<float *>(sbeta)[c] = b;
         if (blockIdx.x == 0) {
             rz_new_out[c] = rzn[c];
@@ -452,14 +274,6 @@ __global__ __launch_bounds__(kBlock) void backward_contract_kernel(const float *
 
 }  // namespace plx
 
-namespace plx {
-int coldot_final(const float *d_partial, int nblocks, int vd, float *d_out, hipStream_t stream)
-{
-    coldot_final_kernel<<<vd, kFinalBlock, 0, stream>>>(d_partial, nblocks, vd, d_out);
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
-}
-}  // namespace plx
 
 using namespace plx;
 
@@ -490,57 +304,23 @@ extern "C" int plx_backward_contract(const float *d_g, const float *d_src, const
 extern "C" int plx_cg_update(float *d_x, float *d_r, const float *d_p, const float *d_ap, const float *d_alpha,
                              int64_t n, int vd, float *d_rs_new, float *d_work, void *stream)
 {
-    if (!d_x || !d_r || !d_p || !d_ap || !d_alpha || !d_rs_new || !d_work) { set_error("plx_cg_update: NULL argument"); return PLX_ERR_INVALID; }
-    if (n < 0 || vd < 1 || vd > kBlock) { set_error("plx_cg_update: vd = %d outside 1..%d", vd, kBlock); return PLX_ERR_INVALID; }
-    const int cw = vd;      // lanes per row
-    hipStream_t s = (hipStream_t)stream;
-    cg_update_kernel<<<kDotBlocks, kBlock, 0, s>>>(d_x, d_r, d_p, d_ap, d_alpha, n, vd, cw, d_work);
-    coldot_final_kernel<<<vd, kFinalBlock, 0, s>>>(d_work, kDotBlocks, vd, d_rs_new);
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
+    return cg_update(cg_rules_f32("plx_cg_update"), d_x, d_r, d_p, d_ap, d_alpha, n, vd, d_rs_new, d_work, (hipStream_t)stream);
 }
 
 extern "C" int plx_cg_step_update(float *d_x, float *d_r, const float *d_p, const float *d_ap, const float *d_rs,
                                   const float *d_pap, const float *d_active, int64_t n, int vd, float *d_rs_new,
                                   float *d_alpha, float *d_work, void *stream)
 {
-    if (!d_x || !d_r || !d_p || !d_ap || !d_rs || !d_pap || !d_active || !d_rs_new || !d_alpha || !d_work) {
-        set_error("plx_cg_step_update: NULL argument");
-        return PLX_ERR_INVALID;
-    }
-    if (n < 0 || vd < 1 || vd > kBlock) { set_error("plx_cg_step_update: vd = %d outside 1..%d", vd, kBlock); return PLX_ERR_INVALID; }
-    const int cw = vd;      // lanes per row
-    hipStream_t s = (hipStream_t)stream;
-    cg_step_update_kernel<<<kDotBlocks, kBlock, 0, s>>>(d_x, d_r, d_p, d_ap, d_rs, d_pap, d_active, n, vd, cw, d_work, d_alpha);
-    coldot_final_kernel<<<vd, kFinalBlock, 0, s>>>(d_work, kDotBlocks, vd, d_rs_new);
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
+    return cg_step_update(cg_rules_f32("plx_cg_step_update"), d_x, d_r, d_p, d_ap, d_rs, d_pap, d_active, n, vd, d_rs_new,
+                          d_alpha, d_work, (hipStream_t)stream);
 }
 
 extern "C" int plx_cg_step_direction(float *d_p, const float *d_r, const float *d_rs_new, const float *d_rs,
                                      const float *d_active, const float *d_b_norm, float tol, int64_t n, int vd,
                                      float *d_beta, float *d_active_out, void *stream)
 {
-    if (!d_p || !d_r || !d_rs_new || !d_rs || !d_active || !d_b_norm || !d_beta || !d_active_out) {
-        set_error("plx_cg_step_direction: NULL argument");
-        return PLX_ERR_INVALID;
-    }
-    if (d_active == d_active_out) { set_error("plx_cg_step_direction: active and active_out must be different buffers"); return PLX_ERR_INVALID; }
-    if (n < 0 || vd < 1 || vd > kBlock) { set_error("plx_cg_step_direction: vd = %d outside 1..%d", vd, kBlock); return PLX_ERR_INVALID; }
-    const int64_t total = n * vd;
-    if (total > 0 && (total & 3) == 0 && ((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_r)) & 15) == 0) {
-        const int64_t quads = total / 4;
-        cg_step_direction4_kernel<<<ceil_div(quads, kBlock), kBlock, 0, (hipStream_t)stream>>>(
-            reinterpret_cast<float4 *>(d_p), reinterpret_cast<const float4 *>(d_r), d_rs_new, d_rs, d_active, d_b_norm, tol,
-            quads, vd, d_beta, d_active_out);
-        PLX_HIP_TRY(hipGetLastError());
-        return PLX_OK;
-    }
-    const int grid = total > 0 ? ceil_div(total, kBlock) : 1;
-    cg_step_direction_kernel<<<grid, kBlock, 0, (hipStream_t)stream>>>(d_p, d_r, d_rs_new, d_rs, d_active, d_b_norm, tol, total,
-                                                                     vd, d_beta, d_active_out);
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
+    return cg_step_direction(cg_rules_f32("plx_cg_step_direction"), d_p, d_r, d_rs_new, d_rs, d_rs_new, d_active, d_b_norm, tol,
+                             n, vd, d_beta, d_active_out, (hipStream_t)stream);
 }
 
 extern "C" int64_t plx_cg_fused_work_floats(int vd) { return (vd >= 4 && vd <= 16 && vd % 4 == 0) ? (int64_t)kFusedBlocks * vd : -1; }
@@ -653,14 +433,7 @@ extern "C" int plx_cg_direction(float *d_p, const float *d_r, const float *d_bet
 extern "C" int plx_coldot(const float *d_a, const float *d_b, int64_t n, int vd, float *d_out, float *d_work,
                           void *stream)
 {
-    if (!d_a || !d_b || !d_out || !d_work) { set_error("plx_coldot: NULL argument"); return PLX_ERR_INVALID; }
-    if (n < 0 || vd < 1 || vd > kBlock) { set_error("plx_coldot: vd = %d outside 1..%d", vd, kBlock); return PLX_ERR_INVALID; }
-    const int cw = vd;      // lanes per row
-    hipStream_t s = (hipStream_t)stream;
-    coldot_partial_kernel<<<kDotBlocks, kBlock, 0, s>>>(d_a, d_b, n, vd, cw, d_work);
-    coldot_final_kernel<<<vd, kFinalBlock, 0, s>>>(d_work, kDotBlocks, vd, d_out);
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
+    return cg_coldot(cg_rules_f32("plx_coldot"), d_a, d_b, n, vd, d_out, d_work, (hipStream_t)stream);
 }
 
 extern "C" int64_t plx_coldot_work_floats(int vd) { return (int64_t)kDotBlocks * (vd > 0 ? vd : 1); }

@@ -11,7 +11,8 @@
 //     pcg_gram_kernel     G = L^T R        MFMA f32 16x16x4 (exact fp32 products, fp32 accumulate), per-workgroup partials
 //     pcg_project_kernel  T = C^-1 G       C = sigma^2 I + L^T L, its inverse precomputed in fp64 [kp][kp]
 //     pcg_apply_kernel    Z = (R - L T) / sigma^2, with the per-workgroup partials of <R, Z> from the same registers
-//   pcg_step_direction   beta = rz' / rz, P = Z + beta P, active' from the TRUE residual norm
+//   plx_pcg_step_direction   beta = rz' / rz, P = Z + beta P, active' from the TRUE residual norm: the direction step of
+//                            plx_cg_kernels.h (plx_linalg.hip holds the fp32 kernels), as is the final sum of <R, Z>
 //
 //   the factor is built in BATCHES of up to 16 speculated pivots (plx_pchol_*): the next nb pivots are the nb largest
 //   entries of the residual diagonal (ties: lower caller row first, as torch.argmax breaks them); their nb kernel
@@ -280,74 +281,6 @@ __global__ __launch_bounds__(kBlock) void pcg_to_half_kernel(const float4 *__res
     const uint32_t lo = (uint32_t)__half_as_ushort(__float2half_rn(v.x)) | ((uint32_t)__half_as_ushort(__float2half_rn(v.y)) << 16);
     const uint32_t hi = (uint32_t)__half_as_ushort(__float2half_rn(v.z)) | ((uint32_t)__half_as_ushort(__float2half_rn(v.w)) << 16);
     dst[q] = make_uint2(lo, hi);
-}
-
-// ---- direction of a preconditioned iteration: beta = active ? rz' / rz : 0; P = Z + beta P; a column stays active
-// while its TRUE residual, sqrt(rr) / |b|, is above tol (rr = |R|^2 from plx_cg_step_update) -------------------------
-__global__ __launch_bounds__(kBlock) void pcg_step_direction_kernel(float *__restrict__ P, const float *__restrict__ Z,
-                                                                    const float *__restrict__ rz_new,
-                                                                    const float *__restrict__ rz,
-                                                                    const float *__restrict__ rr,
-                                                                    const float *__restrict__ active,
-                                                                    const float *__restrict__ b_norm, float tol,
-                                                                    int64_t total, int vd, float *__restrict__ beta_out,
-                                                                    float *__restrict__ active_out)
-{
-    __shared__ float sbeta[kBlock];
-    if ((int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        sbeta[c] = active[c] > 0.f ? rz_new[c] / fmaxf(rz[c], 1e-30f) : 0.f;
-    }
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < total) {
-        const uint32_t uvd = (uint32_t)vd;
-        const uint32_t bm = ((blockIdx.x % uvd) * ((uint32_t)kBlock % uvd)) % uvd;      // wave-uniform
-        const uint32_t c = (bm + threadIdx.x) % uvd;
-        P[i] = Z[i] + P[i] * sbeta[c];
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        const bool on = active[c] > 0.f;
-        beta_out[c] = on ? rz_new[c] / fmaxf(rz[c], 1e-30f) : 0.f;
-        active_out[c] = (on && sqrtf(rr[c]) / b_norm[c] > tol) ? 1.f : 0.f;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void pcg_step_direction4_kernel(float4 *__restrict__ P, const float4 *__restrict__ Z,
-                                                                     const float *__restrict__ rz_new,
-                                                                     const float *__restrict__ rz,
-                                                                     const float *__restrict__ rr,
-                                                                     const float *__restrict__ active,
-                                                                     const float *__restrict__ b_norm, float tol,
-                                                                     int64_t quads, int vd, float *__restrict__ beta_out,
-                                                                     float *__restrict__ active_out)
-{
-    __shared__ float sbeta[kBlock];
-    if ((int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        sbeta[c] = active[c] > 0.f ? rz_new[c] / fmaxf(rz[c], 1e-30f) : 0.f;
-    }
-    __syncthreads();
-    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q < quads) {
-        const uint32_t uvd = (uint32_t)vd;
-        const uint32_t bm = ((blockIdx.x % uvd) * ((4u * (uint32_t)kBlock) % uvd)) % uvd;      // wave-uniform
-        uint32_t c = (bm + 4u * threadIdx.x) % uvd;
-        const float4 z = Z[q];
-        float4 p = P[q];
-        p.x = z.x + p.x * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
-        p.y = z.y + p.y * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
-        p.z = z.z + p.z * sbeta[c]; c = c + 1 == uvd ? 0 : c + 1;
-        p.w = z.w + p.w * sbeta[c];
-        P[q] = p;
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < vd) {
-        const int c = threadIdx.x;
-        const bool on = active[c] > 0.f;
-        beta_out[c] = on ? rz_new[c] / fmaxf(rz[c], 1e-30f) : 0.f;
-        active_out[c] = (on && sqrtf(rr[c]) / b_norm[c] > tol) ? 1.f : 0.f;
-    }
 }
 
 // =====================================================================================================================
@@ -841,7 +774,7 @@ extern "C" int plx_pcg_apply(const void *d_lt, int factor_type, int64_t ld, int 
     const bool half = factor_type == PLX_FACTOR_F16;
     if (half) PLX_TRY((apply_launch<false, true>(d_lt, ld, k, d_r, n, t, d_t, d_scale, d_z, 0, part, s)));
     else PLX_TRY((apply_launch<false, false>(d_lt, ld, k, d_r, n, t, d_t, d_scale, d_z, 0, part, s)));
-    if (d_rz) PLX_TRY(coldot_final(part, ceil_div(n, kBlock * (half ? 2 : 1)), t, d_rz, s));
+    if (d_rz) PLX_TRY(coldot_final(part, ceil_div(n, kBlock * (half ? 2 : 1)), t, t, d_rz, s));
     return PLX_OK;
 }
 
@@ -853,30 +786,14 @@ extern "C" int plx_pcg_rz_partial_rows(int64_t n, int factor_type)
     return ceil_div(n, kBlock * (factor_type == PLX_FACTOR_F16 ? 2 : 1));
 }
 
+// beta = active ? rz' / rz : 0; P = Z + beta P; a column stays active while its TRUE residual, sqrt(rr) / |b|, is above tol
+// (rr = |R|^2 from plx_cg_step_update): plx_cg_kernels.h's direction step with Z as the source
 extern "C" int plx_pcg_step_direction(float *d_p, const float *d_z, const float *d_rz_new, const float *d_rz,
                                       const float *d_rr, const float *d_active, const float *d_b_norm, float tol, int64_t n,
                                       int vd, float *d_beta, float *d_active_out, void *stream)
 {
-    if (!d_p || !d_z || !d_rz_new || !d_rz || !d_rr || !d_active || !d_b_norm || !d_beta || !d_active_out) {
-        set_error("plx_pcg_step_direction: NULL argument");
-        return PLX_ERR_INVALID;
-    }
-    if (d_active == d_active_out) { set_error("plx_pcg_step_direction: active and active_out must be different buffers"); return PLX_ERR_INVALID; }
-    if (n < 0 || vd < 1 || vd > kBlock) { set_error("plx_pcg_step_direction: vd = %d outside 1..%d", vd, kBlock); return PLX_ERR_INVALID; }
-    const int64_t total = n * vd;
-    hipStream_t s = (hipStream_t)stream;
-    if (total > 0 && (total & 3) == 0 && ((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_z)) & 15) == 0) {
-        const int64_t quads = total / 4;
-        pcg_step_direction4_kernel<<<ceil_div(quads, kBlock), kBlock, 0, s>>>(
-            reinterpret_cast<float4 *>(d_p), reinterpret_cast<const float4 *>(d_z), d_rz_new, d_rz, d_rr, d_active, d_b_norm, tol,
-            quads, vd, d_beta, d_active_out);
-    } else {
-        const int grid = total > 0 ? ceil_div(total, kBlock) : 1;
-        pcg_step_direction_kernel<<<grid, kBlock, 0, s>>>(d_p, d_z, d_rz_new, d_rz, d_rr, d_active, d_b_norm, tol, total, vd,
-                                                         d_beta, d_active_out);
-    }
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
+    return cg_step_direction(cg_rules_f32("plx_pcg_step_direction"), d_p, d_z, d_rz_new, d_rz, d_rr, d_active, d_b_norm, tol, n,
+                             vd, d_beta, d_active_out, (hipStream_t)stream);
 }
 
 extern "C" int64_t plx_pchol_work_bytes(int64_t ld, int kp)

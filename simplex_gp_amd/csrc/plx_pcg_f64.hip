@@ -9,8 +9,8 @@
 //                         entries (24 x 53 bits is rounded once, by the fma), fp64 accumulation
 //   pcg64_project_kernel  the partials in workgroup order, then (plx_pcg_project_f64) T = C^-1 G with C^-1 fp64 [kp][kp]
 //   pcg64_apply_kernel    Z = (in_scale R - L T) out_scale, one row per lane, and the workgroup's partial <R, Z>
-// <R, Z> is summed from the apply partials by plx_cg_f64.hip's coldot_final_f64, and plx_pcg_step_direction_f64 (beta =
-// rz' / rz, P = Z + beta P, active' from the TRUE residual norm) is its step_direction_f64.
+// <R, Z> is summed from the apply partials by coldot_final, and plx_pcg_step_direction_f64 (beta = rz' / rz, P = Z + beta P,
+// active' from the TRUE residual norm) is cg_step_direction: plx_cg_kernels.h with T = double, instantiated by plx_cg_f64.hip.
 // Vectors are double [n][t], rows in whatever order the factor's n dimension is in (solvers.LatticePreconditioner64 keeps
 // both in the caller's order, like every fp64 call).  No atomics: partial sums per workgroup, fixed-order final sums.
 #include "plx_internal.h"
@@ -265,7 +265,7 @@ static int check_pcg64(const char *who, const void *lt, int64_t ld, int kp, int6
         return PLX_ERR_INVALID;
     }
     if ((reinterpret_cast<uintptr_t>(lt) & 15) != 0) { set_error("%s: the factor must be 16-byte aligned", who); return PLX_ERR_INVALID; }
-    return check_cg64(who, ptrs, n, t);          // (n and t are inside its ranges by now: the pointer checks remain)
+    return cg_check(cg_rules_f64(who), ptrs, n, t);      // (n and t are inside its ranges by now: the pointer checks remain)
 }
 
 }  // namespace plx
@@ -315,7 +315,7 @@ extern "C" int plx_pcg_apply_f64(const float *d_lt, int64_t ld, int kp, int k, c
     const bool vec = ((reinterpret_cast<uintptr_t>(d_r) | reinterpret_cast<uintptr_t>(d_z)) & 15) == 0;
     if (vec) PLX_TRY(apply64_launch<true>(d_lt, ld, k, d_r, n, t, d_t, d_scale, d_z, part, s));
     else PLX_TRY(apply64_launch<false>(d_lt, ld, k, d_r, n, t, d_t, d_scale, d_z, part, s));
-    if (d_rz) PLX_TRY(coldot_final_f64(part, ceil_div(n, kBlock), t, t, d_rz, s));
+    if (d_rz) PLX_TRY(coldot_final(part, ceil_div(n, kBlock), t, t, d_rz, s));
     return PLX_OK;
 }
 
@@ -323,6 +323,6 @@ extern "C" int plx_pcg_step_direction_f64(double *d_p, const double *d_z, const 
                                           const double *d_rr, const double *d_active, const double *d_b_norm, double tol,
                                           int64_t n, int vd, double *d_beta, double *d_active_out, void *stream)
 {
-    return step_direction_f64("plx_pcg_step_direction_f64", d_p, d_z, d_rz_new, d_rz, d_rr, d_active, d_b_norm, tol, n, vd,
-                              d_beta, d_active_out, (hipStream_t)stream);
+    return cg_step_direction(cg_rules_f64("plx_pcg_step_direction_f64"), d_p, d_z, d_rz_new, d_rz, d_rr, d_active, d_b_norm, tol,
+                             n, vd, d_beta, d_active_out, (hipStream_t)stream);
 }

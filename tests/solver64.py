@@ -1,5 +1,5 @@
 """float64 references, error measures and the kernel-family table for the native solver kernels (plx_linalg.hip,
-plx_pcg.hip, plx_lanczos_kernels.h).  Plain numpy on the CPU: tests/test_solver64.py checks these helpers without a GPU,
+plx_cg_kernels.h, plx_pcg.hip, plx_lanczos_kernels.h).  Plain numpy on the CPU: tests/test_solver64.py checks these helpers without a GPU,
 tests/test_solver_fp64.py holds the kernels against them.
 
 The measure follows lattice64.terms64 / entry_ratio: every output entry is compared with its float64 value in units of
@@ -11,11 +11,11 @@ import re
 
 import numpy as np
 
-TINY = 1e-30            # the max(x, tiny) guard of the CG coefficients (plx_linalg.hip, plx_pcg.hip)
+TINY = 1e-30            # the max(x, tiny) guard of the fp32 CG coefficients (plx_cg_kernels.h: Cg<float>::guard)
 EPS32 = 2.0 ** -24      # half an ulp of fp32, relative
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("plx_linalg.hip", "plx_pcg.hip", "plx_lanczos_kernels.h")
+SOURCES = ("plx_linalg.hip", "plx_cg_kernels.h", "plx_pcg.hip", "plx_lanczos_kernels.h")
 NOT_OURS = ("backward_stack_kernel", "backward_contract_kernel")      # DESIGN section 10 owns them
 
 
@@ -180,7 +180,7 @@ def top_candidates(diag, nb, rank=None):
     return [int(i) for i in sorted(range(d.size), key=lambda i: (-d[i], rank[i]))[:nb]]
 
 
-# ---- which kernels a call runs: the dispatch rules of the three sources, restated ---------------------------------------
+# ---- which kernels a call runs: the dispatch rules of the four sources, restated ---------------------------------------
 K_BLOCK = 256
 DOT_BLOCKS = 1024             # coldot / cg_update / cg_step_update: workgroups = rows of partial sums
 FINAL_BLOCK = 1024
@@ -201,10 +201,11 @@ def coldot_families(kernel):
 
 
 def direction_family(prefix, n, vd, aligned):
-    """plx_cg_step_direction (prefix 'cg') / plx_pcg_step_direction ('pcg'): four elements per thread when n vd is a
-    positive multiple of 4 and both streamed matrices are 16-byte aligned, else the scalar kernel."""
+    """plx_cg_step_direction (prefix 'cg') / plx_pcg_step_direction ('pcg'), one pair of kernels with src = R / Z: four
+    elements per thread when n vd is a positive multiple of 4 and both streamed matrices are 16-byte aligned, else the
+    scalar kernel."""
     total = n * vd
-    return f"{prefix}_step_direction4_kernel" if total > 0 and total % 4 == 0 and aligned else f"{prefix}_step_direction_kernel"
+    return f"step_direction_vec_kernel/{prefix}" if total > 0 and total % 4 == 0 and aligned else f"step_direction_kernel/{prefix}"
 
 
 def fused_family(kernel, vd):
@@ -263,13 +264,13 @@ def _families():
     add("coldot_partial_kernel", "test_coldot")
     add("coldot_final_kernel/tail", "test_coldot, test_cg_updates, test_pcg_apply (d_rz given, up to 3072 partial rows)")
     add("coldot_final_kernel/unrolled", "test_pcg_apply_large (n = 1,100,000, fp32 factor: 4297 partial rows)")
-    add("cg_update_kernel", "test_cg_updates")
-    add("cg_step_update_kernel", "test_cg_updates")
+    add("cg_update_kernel/alpha", "test_cg_updates (plx_cg_update: alpha given)")
+    add("cg_update_kernel/step", "test_cg_updates (plx_cg_step_update: alpha formed on the device)")
     add("cg_direction_kernel", "test_cg_updates")
-    add("cg_step_direction_kernel", "test_step_direction (n vd odd, or P 4 bytes past a 16-byte boundary)")
-    add("cg_step_direction4_kernel", "test_step_direction (n vd a multiple of 4, aligned)")
-    add("pcg_step_direction_kernel", "test_step_direction")
-    add("pcg_step_direction4_kernel", "test_step_direction")
+    add("step_direction_kernel/cg", "test_step_direction (n vd odd, or P 4 bytes past a 16-byte boundary)")
+    add("step_direction_vec_kernel/cg", "test_step_direction (n vd a multiple of 4, aligned)")
+    add("step_direction_kernel/pcg", "test_step_direction")
+    add("step_direction_vec_kernel/pcg", "test_step_direction")
     for nch in (1, 2, 3, 4):
         add(f"cg_step_update_fused_kernel<{nch}>", f"test_fused_steps (vd = {4 * nch})")
         add(f"cg_step_direction_fused_kernel<{nch}>", f"test_fused_steps (vd = {4 * nch})")

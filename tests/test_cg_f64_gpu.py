@@ -67,7 +67,7 @@ def axpy_ld(y, a, x):
 
 def direction_kernel(n, vd, off):
     """plx_cg_step_direction_f64: two elements per thread when n vd is even and both matrices are 16-byte aligned."""
-    return "step_direction64_pair_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "step_direction64_kernel"
+    return "step_direction_vec_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "step_direction_kernel"
 
 
 def work_doubles(vd):
@@ -98,8 +98,8 @@ def test_vector_kernels(n, vd):
         nv.check(lib.plx_coldot_f64(A.ptr, B_.ptr, n, vd, out.ptr, work.ptr, stream()), "plx_coldot_f64")
         want, T = colsum_ld(a, b)
         e = entry_ratio(out.np(), want, T)
-        note("coldot64_partial_kernel", e, (n + 4) * U2)
-        REACHED.add("coldot64_final_kernel")
+        note("coldot_partial_kernel", e, (n + 4) * U2)
+        REACHED.add("coldot_final_kernel")
         assert e <= (n + 4) * U2, (label, "coldot", e)
         first = out.cpu().clone()
         nv.check(lib.plx_coldot_f64(A.ptr, B_.ptr, n, vd, out.ptr, work.ptr, stream()), "plx_coldot_f64")
@@ -127,16 +127,16 @@ def test_vector_kernels(n, vd):
         gx, gr = gx.reshape(n, vd), gr.reshape(n, vd)
         alpha_want = np.where(act > 0, np.asarray(np.asarray(rs, LD) / np.maximum(np.asarray(pap, LD), TINY64), np.float64), 0.0)
         ea = rel_ratio(ga, alpha_want)
-        note("cg64_step_update_kernel", ea, 4 * U2)
+        note("cg_update_kernel", ea, 4 * U2)
         assert ea <= 4 * U2, (label, "alpha", ea)
         wx, Tx = axpy_ld(x0, ga, p0)                         # from the alpha the kernel formed
         wr, Tr = axpy_ld(r0, -ga, ap0)
         ex, er = entry_ratio(gx, wx, Tx), entry_ratio(gr, wr, Tr)
-        note("cg64_step_update_kernel", max(ex, er), 4 * U2)
+        note("cg_update_kernel", max(ex, er), 4 * U2)
         assert ex <= 4 * U2 and er <= 4 * U2, (label, "X / R", ex, er)
         wrs, Trs = colsum_ld(gr, gr)                         # |R|^2 of the R the kernel stored
         ers = entry_ratio(grs, wrs, Trs)
-        note("cg64_step_update_kernel", ers, (n + 4) * U2)
+        note("cg_update_kernel", ers, (n + 4) * U2)
         assert ers <= (n + 4) * U2, (label, "rs_new", ers)
         if inactive is not None:
             assert ga[inactive] == 0.0
@@ -408,7 +408,7 @@ def test_solve_with_fused_dot():
               f"residual {res:.2e}")
         assert res <= 1e-10, (native, res)
     assert abs(its[True] - its[False]) <= check_every, its
-    REACHED.update(("cg64_step_update_kernel", "coldot64_partial_kernel", "coldot64_final_kernel"))
+    REACHED.update(("cg_update_kernel", "coldot_partial_kernel", "coldot_final_kernel"))
     lat.close()
 
 
@@ -481,18 +481,18 @@ def report():
 
 
 def test_every_new_kernel_was_launched():
-    """Every __global__ kernel of plx_cg_f64.hip ran in this module (run as a whole), and the slice names it reports are
-    the three the affine cases expect."""
+    """Every __global__ kernel of plx_cg_f64.hip and of plx_cg_kernels.h, the templated vector steps it instantiates for
+    double, ran in this module (run as a whole), and the slice names it reports are the three the affine cases expect."""
     print(report())
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "simplex_gp_amd", "csrc", "plx_cg_f64.hip")).read()
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "simplex_gp_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, src)).read() for src in ("plx_cg_f64.hip", "plx_cg_kernels.h"))
     text = re.sub(r"//[^\n]*", "", text)
     kernels = set(re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s*)?void\s+(\w+)\s*\(", text))
     literals = set()
     for stmt in re.finditer(r"\bkn_f64_slice\s*=([^;]*);", text):
         literals.update(re.findall(r'"([^"]*)"', stmt.group(1)))
     assert literals == {AFF_V1, AFF_CHUNK, AFF_WIDE}, literals
-    assert kernels == {"coldot64_partial_kernel", "coldot64_final_kernel", "cg64_step_update_kernel",
-                       "step_direction64_kernel", "step_direction64_pair_kernel", AFF_V1, AFF_CHUNK, AFF_WIDE}, kernels
+    assert kernels == {"coldot_partial_kernel", "coldot_final_kernel", "cg_update_kernel",
+                       "step_direction_kernel", "step_direction_vec_kernel", AFF_V1, AFF_CHUNK, AFF_WIDE}, kernels
     assert kernels <= REACHED, sorted(kernels - REACHED)
     assert all(v <= 1.0 for v in WORST.values()), WORST

@@ -76,7 +76,7 @@ def factor(rng, n, k, kp):
 
 
 def direction_kernel(n, vd, off):
-    return "step_direction64_pair_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "step_direction64_kernel"
+    return "step_direction_vec_kernel" if (n * vd) % 2 == 0 and off % 2 == 0 else "step_direction_kernel"
 
 
 def bits(t):
@@ -162,7 +162,7 @@ def test_pcg64_kernels(n, k, kp):
             assert e <= (k + 6) * U2, (label, "apply", e)
             prod = ld_(r) * ld_(z)
             e = entry_ratio(rz, f64_(prod.sum(0)), f64_(np.abs(prod).sum(0)))
-            note("coldot64_final_kernel", e, (n + 4) * U2)
+            note("coldot_final_kernel", e, (n + 4) * U2)
             assert e <= (n + 4) * U2, (label, "rz", e)
             # rz = NULL: the same Z
             Z2 = Buf(count=n * t, offset=off, dtype=F64)
@@ -206,7 +206,7 @@ def test_pcg64_kernels(n, k, kp):
 
 def test_apply_large_reaches_the_unrolled_final_sum():
     """n = 786,689 at kp = 16, k = 1, t = 2: <R, Z> has 3074 partial rows (one per 256 rows), more than 3 * 1024, so
-    coldot64_final_kernel's four-way unrolled loop runs -- plx_coldot_f64 always hands it 1024 rows.  The <R, Z> bar of
+    coldot_final_kernel's four-way unrolled loop runs -- plx_coldot_f64 always hands it 1024 rows.  The <R, Z> bar of
     test_pcg64_kernels, (n + 4) U2 on the entry ratio against longdouble from the device's own Z."""
     lib = nv.lib()
     n, k, kp, t = 786_689, 1, 16, 2
@@ -232,7 +232,7 @@ def test_apply_large_reaches_the_unrolled_final_sum():
     assert e <= (k + 6) * U2, ("apply", e)
     prod = ld_(r) * ld_(z)
     e = entry_ratio(rz, f64_(prod.sum(0)), f64_(np.abs(prod).sum(0)))
-    note("coldot64_final_kernel", e, (n + 4) * U2)
+    note("coldot_final_kernel", e, (n + 4) * U2)
     print(f"<R, Z> over 3074 partial rows: error / ((n + 4) U2) = {e / ((n + 4) * U2):.4f}")
     assert e <= (n + 4) * U2, ("rz", e)
 
@@ -626,15 +626,15 @@ def report():
 
 def test_every_new_kernel_was_launched():
     """Every __global__ kernel of plx_pcg_f64.hip, every column count of the apply pass and the three kernels of
-    plx_cg_f64.hip that this file's entry points launch (the final sum of <R, Z>, the two direction forms) ran in this module
-    (run as a whole), under its bar."""
+    plx_cg_kernels.h that this file's entry points launch (the final sum of <R, Z>, the two direction forms) ran in this
+    module (run as a whole), under its bar."""
     print(report())
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "simplex_gp_amd", "csrc", "plx_pcg_f64.hip")).read()
-    text = re.sub(r"//[^\n]*", "", text)
-    kernels = set(re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s*)?void\s+(\w+)\s*\(", text))
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "simplex_gp_amd", "csrc")
+    find = r"__global__\s+(?:__launch_bounds__\([^)]*\)\s*)?void\s+(\w+)\s*\("
+    kernels = set(re.findall(find, re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "plx_pcg_f64.hip")).read())))
     assert kernels == {"pcg64_gram_kernel", "pcg64_project_kernel", "pcg64_apply_kernel"}, kernels
-    shared = {"coldot64_final_kernel", "step_direction64_kernel", "step_direction64_pair_kernel"}
+    shared = {"coldot_final_kernel", "step_direction_kernel", "step_direction_vec_kernel"}
+    assert shared <= set(re.findall(find, re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "plx_cg_kernels.h")).read())))
     reached = {k.split("<")[0] for k in REACHED}
     assert kernels | shared <= reached, sorted((kernels | shared) - reached)
     assert {f"pcg64_apply_kernel<{t}>" for t in TS} <= REACHED

@@ -130,28 +130,28 @@ def test_pchol64_is_the_pivoted_cholesky():
 def test_dispatch_rules():
     assert s64.final_family(1024) == s64.final_family(3072) == "coldot_final_kernel/tail"
     assert s64.final_family(3073) == "coldot_final_kernel/unrolled"
-    assert s64.direction_family("cg", 4099, 3, True) == "cg_step_direction_kernel"
-    assert s64.direction_family("cg", 4100, 3, True) == "cg_step_direction4_kernel"
-    assert s64.direction_family("pcg", 4100, 16, False) == "pcg_step_direction_kernel"
-    assert s64.direction_family("pcg", 0, 4, True) == "pcg_step_direction_kernel"
+    assert s64.direction_family("cg", 4099, 3, True) == "step_direction_kernel/cg"
+    assert s64.direction_family("cg", 4100, 3, True) == "step_direction_vec_kernel/cg"
+    assert s64.direction_family("pcg", 4100, 16, False) == "step_direction_kernel/pcg"
+    assert s64.direction_family("pcg", 0, 4, True) == "step_direction_kernel/pcg"
     assert s64.gram_families(16, False) == ["pcg_gram_kernel<1,f32>"]
     assert s64.gram_families(144, True) == ["pcg_gram_kernel<8,f16>", "pcg_gram_kernel<1,f16>"]
     assert s64.gram_families(400, False) == ["pcg_gram_kernel<8,f32>"] * 3 + ["pcg_gram_kernel<1,f32>"]
     assert s64.rz_rows(1_100_000, False) == 4297 and s64.rz_rows(513, True) == 2
     assert [s64.lanczos_span(n) for n in (1, 65_536, 65_537, 262_144, 262_145, 1_048_576, 1_048_577, 2_097_152, 2_097_153)] == \
         [256, 256, 1024, 1024, 4096, 4096, 8192, 8192, None]
-    for fams in (s64.coldot_families("cg_update_kernel"), s64.project_families(1008, True), s64.apply_families(5, 16, True, True),
+    for fams in (s64.coldot_families("cg_update_kernel/alpha"), s64.project_families(1008, True), s64.apply_families(5, 16, True, True),
                  s64.pchol_batch_families(3, 7, 7, 1), s64.lanczos_families(70_000), [s64.fused_family("cg_step_update_fused_kernel", 12)]):
         assert set(fams) <= set(s64.FAMILIES), fams
 
 
 def test_solver_families_name_every_kernel_and_template_value():
-    """Every __global__ kernel of plx_linalg.hip, plx_pcg.hip and plx_lanczos_kernels.h (but the two backward kernels DESIGN
-    section 10 owns) and every template value their switch statements and PLX_*_CASE lists dispatch is a family of
+    """Every __global__ kernel of plx_linalg.hip, plx_cg_kernels.h, plx_pcg.hip and plx_lanczos_kernels.h (but the two backward
+    kernels DESIGN section 10 owns) and every template value their switch statements and PLX_*_CASE lists dispatch is a family of
     solver64.FAMILIES, and FAMILIES names no kernel the sources do not have: a new kernel or value fails here until a case
     reaches it."""
     kernels, pairs = s64.parse_sources()
-    assert len(kernels) >= 29 and len(pairs) >= 52
+    assert len(kernels) >= 26 and len(pairs) >= 52      # (26: the CG vector steps are five templated kernels, once)
     ours = kernels - set(s64.NOT_OURS)
     named = {s64.family_kernel(f) for f in s64.FAMILIES}
     assert named == ours, {"in the sources only": sorted(ours - named), "in FAMILIES only": sorted(named - ours)}

@@ -1,4 +1,4 @@
-"""The native solver kernels (plx_linalg.hip, plx_pcg.hip, plx_lanczos_kernels.h) against float64, at every kernel family.
+"""The native solver kernels (plx_linalg.hip, plx_cg_kernels.h, plx_pcg.hip, plx_lanczos_kernels.h) against float64, at every kernel family.
 
 Every case calls the C ABI on fp32 data it made itself, evaluates the same expression in float64 on the CPU from the
 same fp32 values (tests/solver64.py) and judges every output entry in units of the terms it sums.  The family a call
@@ -174,7 +174,7 @@ def test_cg_updates(lib, n, vd):
     rsn, work = Buf(count=vd), Buf(count=int(lib.plx_coldot_work_floats(vd)))
     ok(lib.plx_cg_update(X.ptr, R.ptr, P.ptr, AP.ptr, AL.ptr, n, vd, rsn.ptr, work.ptr, stream()), "plx_cg_update")
     check_buffers([P, AP, AL], [X, R, rsn, work])
-    fams = s64.coldot_families("cg_update_kernel")
+    fams = s64.coldot_families("cg_update_kernel/alpha")
     _check_axpy(fams, f"cg_update X n={n} vd={vd}", X.np(n, vd), x.numpy(), alpha.numpy(), p.numpy())
     _check_axpy(fams, f"cg_update R n={n} vd={vd}", R.np(n, vd), r.numpy(), -alpha.numpy(), ap.numpy())
     want, T = s64.coldot64(R.np(n, vd), R.np(n, vd))
@@ -185,7 +185,7 @@ def test_cg_updates(lib, n, vd):
     ok(lib.plx_cg_step_update(X.ptr, R.ptr, P.ptr, AP.ptr, RS.ptr, PAP.ptr, ACT.ptr, n, vd, rsn.ptr, al.ptr, work.ptr, stream()),
        "plx_cg_step_update")
     check_buffers([P, AP, RS, PAP, ACT], [X, R, rsn, al, work])
-    fams = s64.coldot_families("cg_step_update_kernel")
+    fams = s64.coldot_families("cg_update_kernel/step")
     frozen = active.numpy() == 0
     a_dev = al.np()
     assert np.all(a_dev[frozen] == 0)
@@ -252,6 +252,40 @@ def test_step_direction(lib, which, n, vd, off):
     flag, decided = s64.active64(active.numpy(), res.numpy(), b_norm.numpy(), tol)
     assert decided.all(), "a flag of this case would be decided by rounding: move the data away from tol"
     assert torch.equal(act_out.cpu(), torch.from_numpy(flag))
+
+
+@pytest.mark.parametrize("vd", (3, 12))
+@pytest.mark.parametrize("n", (1, 257))
+def test_cg_direction_is_the_pcg_direction(lib, n, vd):
+    """plx_cg_step_direction(P, R, rs_new, rs, ...) is plx_pcg_step_direction(P, R, rs_new, rs, rr = rs_new, ...): P, beta
+    and active_out agree bit for bit, P aligned and offset by one float (the vector and the scalar form each way: n vd is
+    a multiple of 4 only at vd = 12), one column inactive and the others on either side of tol."""
+    g = rng("cg is pcg", n, vd)
+    p, r = torch.randn(n, vd, generator=g), torch.randn(n, vd, generator=g)
+    rs_new, rs = (torch.rand(vd, generator=g) * 1.5 + 0.5) * n, (torch.rand(vd, generator=g) * 1.5 + 0.5) * n
+    tol = 1e-3
+    b_norm = (rs_new.double().sqrt() / tol * torch.where(torch.arange(vd) % 2 == 0, 0.5, 2.0)).float()
+    active = torch.ones(vd)
+    active[vd // 2] = 0
+    for off in (0, 1):
+        RSN, RS, ACT, BN = Buf(rs_new), Buf(rs), Buf(active), Buf(b_norm)
+        outs = []
+        for which in ("cg", "pcg"):
+            P, R = Buf(p, offset=off), Buf(r)
+            beta, act_out = Buf(count=vd), Buf(count=vd)
+            if which == "cg":
+                ok(lib.plx_cg_step_direction(P.ptr, R.ptr, RSN.ptr, RS.ptr, ACT.ptr, BN.ptr, tol, n, vd, beta.ptr, act_out.ptr,
+                                             stream()), "plx_cg_step_direction")
+            else:
+                ok(lib.plx_pcg_step_direction(P.ptr, R.ptr, RSN.ptr, RS.ptr, RSN.ptr, ACT.ptr, BN.ptr, tol, n, vd, beta.ptr,
+                                              act_out.ptr, stream()), "plx_pcg_step_direction")
+            check_buffers([R, RSN, RS, ACT, BN], [P, beta, act_out])
+            reached(s64.direction_family(which, n, vd, off % 4 == 0))
+            outs.append((P.cpu(), beta.cpu(), act_out.cpu()))
+        for name, u, v in zip(("P", "beta", "active_out"), *outs):
+            assert _bits_equal(u, v), (n, vd, off, name)
+        gp, gb, gact = outs[0]
+        assert not torch.equal(gp, p.reshape(-1)) and set(gact.tolist()) == {0.0, 1.0} and gb[vd // 2] == 0.0
 
 
 # ---- the fused pair and the preconditioned fused direction ------------------------------------------------------------------

@@ -16,6 +16,8 @@ The MVM in double is dominated by the fp64 splat on coarse lattices (DESIGN.md s
 hides the vector work in the full-iteration columns; the two "vectors" columns are what this change is about.
 
     python tools/cg_f64_time.py [--out profiles/cg_f64_time.md] [--rounds 7] [--calls 20]
+    python tools/cg_f64_time.py --fp32 [--rounds 7] [--calls 20]      the fp32 vector calls alone (plx_coldot + plx_cg_step_update
+                                                                     + plx_cg_step_direction), n of the three shapes, vd = 11 and 12
 
 Shapes: N = 1e6, d = 8, order 1 (the headline build); N = 2e4, d = 4, order 1; the config-5 stand-in (MaternLattice nu = 1.5,
 order 3, N = 10,623, d = 18).  Needs a GPU: there is no CPU timing.
@@ -102,14 +104,47 @@ class Iteration:
         self.torch_vectors()
 
 
+def fp32_vectors(rounds, calls):
+    """The fp32 twins of "native vectors": plx_coldot + plx_cg_step_update + plx_cg_step_direction on [n][vd] floats, n of
+    the three shapes, vd = 11 (the scalar direction kernel at odd n) and 12 (the vector one); no lattice is needed."""
+    lib, dev = nv.lib(), torch.device("cuda", 0)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())          # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    print("| n | vd | fp32 vectors ms (spread) |\n|---|---|---|")
+    for n in (1_000_000, 20_000, 10_623):
+        for vd in (11, 12):
+            g = torch.Generator().manual_seed(n + vd)
+            X, R, P, AP = (torch.randn(n, vd, generator=g).to(dev) for _ in range(4))
+            rs, b_norm, active = (R * R).sum(0), R.norm(dim=0), torch.ones(vd, device=dev)
+            pap = (P * AP).sum(0).abs() * 1e12 + 1.0          # alpha ~ 1e-12: the vectors move by rounding-level amounts only
+            rs_new, alpha, beta, active_next = (torch.empty(vd, device=dev) for _ in range(4))
+            work = torch.empty(int(lib.plx_coldot_work_floats(vd)), device=dev)
+
+            def step():
+                nv.check(lib.plx_coldot(p(P), p(AP), n, vd, p(rs_new), p(work), st), "plx_coldot")
+                nv.check(lib.plx_cg_step_update(p(X), p(R), p(P), p(AP), p(rs), p(pap), p(active), n, vd, p(rs_new), p(alpha), p(work),
+                                                st), "plx_cg_step_update")
+                nv.check(lib.plx_cg_step_direction(p(P), p(R), p(rs_new), p(rs), p(active), p(b_norm), 0.0, n, vd, p(beta),
+                                                   p(active_next), st), "plx_cg_step_direction")
+            for _ in range(3):
+                step()
+            torch.cuda.synchronize()
+            times = [timed(step, calls) for _ in range(rounds)]
+            assert bool(torch.isfinite(X).all() and torch.isfinite(P).all())
+            print(f"| {n} | {vd} | {min(times):.4f} ({(max(times) - min(times)) / min(times) * 100:.1f} %) |", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--fp32", action="store_true", help="time the fp32 vector calls alone (no lattice, no torch route)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("cg_f64_time.py needs a GPU: a CPU run says nothing about these kernels")
+    if args.fp32:
+        return fp32_vectors(args.rounds, args.calls)
     dev = torch.device("cuda", 0)
     headline = np.array([0.34608543, 1.0, 0.34608543], np.float32)
     taps5 = plx.MaternLattice(nu=1.5, order=3, ard_num_dims=18).dkernel_fn.get_coeffs().numpy()
