@@ -549,6 +549,39 @@ int plx_locate_pullback(plx_lattice *lat, const float *d_x, const float *d_t, in
 int plx_locate_pullback_f64(plx_lattice *lat, const float *d_x, const double *d_t, int64_t nq, double *d_gx, void *stream);
 
 /*
+ * The splat at query points (callers detect it by symbol; the version string is unchanged): S*^T g, the query twin of
+ * plx_splat and the adjoint of plx_slice_at without its 1 / (1 + 2^-d),
+ *     values[v][c] = sum over the corners (r, q) with d_vid[r][q] == v of d_w[r][q] g[q][c].
+ * With plx_blur_t / plx_blur_t_f64 and plx_slice / plx_slice_f64 after it, it is K_q^T g = K(X, x*) g; the call carries no
+ * scaling flag.  Two steps, no atomics:
+ *   plx_query_plan_bytes  the bytes a plan of nq queries needs on the current build (a function of m, d and nq alone); -1
+ *                 for an unbuilt lattice, nq < 1 or nq * (d + 1) >= 2^31 - 4096.
+ *   plx_query_plan  once per located query (d_vid, d_w as plx_locate left them): the nq (d + 1) corner pairs, pair index
+ *                 r * nq + q, sorted by vertex with a stable sort; an absent corner (id -1) and an id outside [0, m) sort
+ *                 behind every vertex and index nothing.  d_plan: plx_query_plan_bytes bytes, 16-byte aligned, the
+ *                 caller's; it holds the sorted tables AND the sort's scratch, so no buffer of the lattice is touched.
+ *                 Inside a vertex the corners stand in ascending pair index: that is the summation order of the splat,
+ *                 and two plans of one query are equal byte for byte in their tables.
+ *   plx_splat_at / plx_splat_at_f64
+ *                 d_g [nq][vd], dense; d_values [m][plx_values_stride(vd)] / [m][plx_values_stride_f64(vd)], 16-byte
+ *                 aligned for vd > 1.  EVERY row is written: exact zeros at a vertex no query corner lands on and in the
+ *                 stride padding.  One launch of the kernels of plx_splat_rows / plx_splat_rows_f64, the family chosen by
+ *                 the row width alone; a vertex sums fma(w, g, acc) over its corners in plan order.
+ *   plx_last_splat_at_kernels  "plan=...;splat_at=..." of the last such calls.
+ * The library CANNOT tell whether a plan was made on this build or for this nq: a plan of another build or another nq
+ * is read as if it were right (simplex_gp_amd.query_adjoint.QueryPlan carries both and refuses).  Launches only: no
+ * allocation, no read-back, legal under stream capture.  Refusals, all before the first launch, the outputs untouched:
+ * those of plx_slice_at, an output that overlaps an input or the plan among them (PLX_ERR_INVALID), and
+ * nq * (d + 1) >= 2^31 - 4096, the sort's limit (PLX_ERR_TOO_LARGE).
+ */
+int64_t plx_query_plan_bytes(const plx_lattice *lat, int64_t nq);
+int plx_query_plan(plx_lattice *lat, const int32_t *d_vid, const float *d_w, int64_t nq, void *d_plan, void *stream);
+int plx_splat_at(plx_lattice *lat, const void *d_plan, const float *d_g, int vd, int64_t nq, float *d_values, void *stream);
+int plx_splat_at_f64(plx_lattice *lat, const void *d_plan, const double *d_g, int vd, int64_t nq, double *d_values,
+                     void *stream);
+int plx_last_splat_at_kernels(const plx_lattice *lat, char *buf, int cap);
+
+/*
  * The float64 position gradient (callers detect it by symbol; the version string is unchanged): plx_apply_backward with
  * every array in double, for every column count.  `lat` is built with the DERIVATIVE taps on the positions rounded to
  * float, as for every fp64 call; d_x [n][d] is the caller's FLOAT64 position matrix (not the rounded copy), d_g (the

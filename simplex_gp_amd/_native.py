@@ -101,6 +101,11 @@ _SIGNATURES = {
     "plx_slice_at_dots_f64": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp]),
     "plx_locate_pullback": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "plx_locate_pullback_f64": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "plx_query_plan_bytes": (_i64, [_vp, _i64]),
+    "plx_query_plan": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "plx_splat_at": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "plx_splat_at_f64": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "plx_last_splat_at_kernels": (_i32, [_vp, ctypes.c_char_p, _i32]),
     "plx_backward_splat_f64": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "plx_backward_contract_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "plx_apply_backward_f64": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
@@ -189,7 +194,8 @@ OPTIONAL_SYMBOLS = frozenset(("plx_pcg_work_doubles", "plx_pcg_gram_f64", "plx_p
                               "plx_blur_sym", "plx_apply_sym", "plx_apply_affine_sym", "plx_last_sym_kernels",
                               "plx_diag", "plx_diag_f64", "plx_locate", "plx_slice_at", "plx_slice_at_f64",
                               "plx_last_query_kernels", "plx_slice_at_dots", "plx_slice_at_dots_f64",
-                              "plx_locate_pullback", "plx_locate_pullback_f64"))
+                              "plx_locate_pullback", "plx_locate_pullback_f64", "plx_query_plan_bytes", "plx_query_plan",
+                              "plx_splat_at", "plx_splat_at_f64", "plx_last_splat_at_kernels"))
 
 
 def declared_symbols():

@@ -1165,6 +1165,92 @@ int plx_last_query_kernels(const plx_lattice *L, char *buf, int cap)
     return PLX_OK;
 }
 
+// ---- the splat at query points (plx_query_adjoint.hip) -------------------------------------------------------------------
+
+// nq (d + 1) corner pairs within the sort's limit
+static int check_plan_pairs(const plx_lattice *L, int64_t nq, const char *who)
+{
+    if (nq * (L->d + 1) >= (1ll << 31) - 4096) {
+        set_error("%s: nq*(d+1) exceeds the 2^31 - 4096 pairs one sort takes; split the queries", who);
+        return PLX_ERR_TOO_LARGE;
+    }
+    return PLX_OK;
+}
+
+int64_t plx_query_plan_bytes(const plx_lattice *L, int64_t nq)
+{
+    if (!L || !L->built || nq < 1 || nq * (L->d + 1) >= (1ll << 31) - 4096) return -1;
+    return query_plan_bytes(L->m, L->d, nq);
+}
+
+int plx_query_plan(plx_lattice *L, const int32_t *d_vid, const float *d_w, int64_t nq, void *d_plan, void *stream)
+{
+    const char *who = "plx_query_plan";
+    EntryScope sc(L, stream);
+    if (!L || !d_vid || !d_w || !d_plan) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (nq < 1) { set_error("%s: nq = %lld must be positive", who, (long long)nq); return PLX_ERR_INVALID; }
+    if ((((uintptr_t)d_vid | (uintptr_t)d_w) & 3) != 0 || ((uintptr_t)d_plan & 15) != 0) {
+        set_error("%s: d_vid and d_w must be 4-byte aligned, d_plan 16-byte aligned", who);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_query_lattice(L, who));
+    PLX_TRY(check_plan_pairs(L, nq, who));
+    const size_t ne = (size_t)nq * (L->d + 1) * 4, np = (size_t)query_plan_bytes(L->m, L->d, nq);
+    if (ranges_overlap(d_plan, np, d_vid, ne) || ranges_overlap(d_plan, np, d_w, ne)) {
+        set_error("%s: d_plan must not overlap d_vid or d_w", who);
+        return PLX_ERR_INVALID;
+    }
+    DeviceGuard g(L->device);
+    return query_plan_impl(L, d_vid, d_w, nq, d_plan, (hipStream_t)stream);
+}
+
+// Everything a splat_at call checks before its one launch.  `esz`: bytes of a value; `stride`: elements of a vertex row.
+static int check_splat_at(const plx_lattice *L, const void *d_plan, const void *d_g, int vd, int64_t nq, const void *d_values,
+                          size_t esz, int stride, const char *who)
+{
+    if (!L || !d_plan || !d_g || !d_values) { set_error("%s: NULL argument", who); return PLX_ERR_INVALID; }
+    if (nq < 1) { set_error("%s: nq = %lld must be positive", who, (long long)nq); return PLX_ERR_INVALID; }
+    if (vd < 1) { set_error("%s: vd = %d must be positive", who, vd); return PLX_ERR_INVALID; }
+    if (((uintptr_t)d_plan & 15) != 0 || (((uintptr_t)d_g | (uintptr_t)d_values) & (esz - 1)) != 0) {
+        set_error("%s: d_plan must be 16-byte aligned, d_g and d_values aligned to their element size", who);
+        return PLX_ERR_INVALID;
+    }
+    PLX_TRY(check_values_aligned(d_values, vd, who));
+    PLX_TRY(check_query_lattice(L, who));
+    PLX_TRY(check_size(L, stride, nq, "nq", who));
+    PLX_TRY(check_plan_pairs(L, nq, who));
+    const size_t ng = (size_t)nq * vd * esz, nv = (size_t)L->m * stride * esz, np = (size_t)query_plan_bytes(L->m, L->d, nq);
+    if (ranges_overlap(d_values, nv, d_g, ng) || ranges_overlap(d_values, nv, d_plan, np)) {
+        set_error("%s: d_values must not overlap d_g or d_plan", who);
+        return PLX_ERR_INVALID;
+    }
+    return PLX_OK;
+}
+
+int plx_splat_at(plx_lattice *L, const void *d_plan, const float *d_g, int vd, int64_t nq, float *d_values, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_splat_at(L, d_plan, d_g, vd, nq, d_values, sizeof(float), vd >= 1 ? values_stride(vd) : 1, "plx_splat_at"));
+    DeviceGuard g(L->device);
+    return splat_at_impl<float>(L, d_plan, d_g, vd, nq, d_values, (hipStream_t)stream);
+}
+
+int plx_splat_at_f64(plx_lattice *L, const void *d_plan, const double *d_g, int vd, int64_t nq, double *d_values, void *stream)
+{
+    EntryScope sc(L, stream);
+    PLX_TRY(check_splat_at(L, d_plan, d_g, vd, nq, d_values, sizeof(double), vd >= 1 ? values_stride_f64(vd) : 1,
+                           "plx_splat_at_f64"));
+    DeviceGuard g(L->device);
+    return splat_at_impl<double>(L, d_plan, d_g, vd, nq, d_values, (hipStream_t)stream);
+}
+
+int plx_last_splat_at_kernels(const plx_lattice *L, char *buf, int cap)
+{
+    if (!L || !buf || cap < 1) return PLX_ERR_INVALID;
+    snprintf(buf, (size_t)cap, "plan=%s;splat_at=%s", L->kn_plan, L->kn_splat_at);
+    return PLX_OK;
+}
+
 // ---- the float64 rectangular product (kernels: plx_rows_f64.hip; tables: plx_rows.hip; blur: plx_f64.hip) --------------
 
 // check_rows and check_f64 in one: the checks of both, each once.

@@ -318,6 +318,8 @@ struct plx_lattice {
     // queries at points that are not the build's (plx_locate in plx_build.hip, plx_slice_at in plx_query_kernels.h)
     const char *kn_locate = "", *kn_slice_at = "";   // kernels of the last query calls (plx_last_query_kernels)
     const char *kn_dots = "", *kn_pullback = "";     // ... and of the last plx_slice_at_dots* / plx_locate_pullback*
+    // ... and of the last plx_query_plan / plx_splat_at* (plx_query_adjoint.hip; plx_last_splat_at_kernels)
+    const char *kn_plan = "", *kn_splat_at = "";
 };
 
 namespace plx {
@@ -410,6 +412,21 @@ int slice_rows_impl(plx_lattice *L, const float *d_values, int vd, int64_t begin
 plx_lattice::RowsRange *range_slot(plx_lattice *L, int64_t begin, int64_t count);
 int ensure_rows_splat(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream);
 int ensure_rows_slice(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t stream);
+// ... and the launch halves, which know nothing of ranges (shared with the splat at query points, plx_query_adjoint.hip):
+// ptr[u] = the first of `kept` ascending vertex ids that is >= u, u = 0..m (rows_ptr_kernel), and values[m][stride(vd)] =
+// the sums of w[j] * src[row[j]] over [ptr[v], ptr[v + 1]) in one launch of the family the row width picks, whose name
+// is returned (the caller asks hipGetLastError)
+void rows_ptr_launch(const int *vid, int kept, int m, int *ptr, hipStream_t stream);
+const char *splat_rows_launch(const int *ptr, const int *row, const float *w, const float *d_src, int vd, int m, float *d_values,
+                              hipStream_t stream);
+const char *splat_rows_f64_launch(const int *ptr, const int *row, const float *w, const double *d_src, int vd, int m,
+                                  double *d_values, hipStream_t stream);
+// plx_query_adjoint.hip: the plan of a located query (its found corners sorted by vertex, laid out in the caller's buffer)
+// and the splat over it (arguments checked by the entry points).  Launches only.
+int64_t query_plan_bytes(int64_t m, int d, int64_t nq);
+int query_plan_impl(plx_lattice *L, const int32_t *d_vid, const float *d_w, int64_t nq, void *d_plan, hipStream_t stream);
+template <typename T>
+int splat_at_impl(plx_lattice *L, const void *d_plan, const T *d_g, int vd, int64_t nq, T *d_values, hipStream_t stream);
 // plx_rows_f64.hip: the same two stages on buffers of doubles, over the same tables
 int splat_rows_f64_impl(plx_lattice *L, const double *d_src, int64_t begin, int64_t count, int vd, double *d_values,
                         hipStream_t stream);

@@ -121,6 +121,11 @@ __global__ __launch_bounds__(kBlock) void rows_ptr_kernel(const int *__restrict_
     ptr[u] = lo;
 }
 
+void rows_ptr_launch(const int *vid, int kept, int m, int *ptr, hipStream_t stream)
+{
+    rows_ptr_kernel<<<ceil_div((int64_t)m + 1, kBlock), kBlock, 0, stream>>>(vid, kept, m, ptr);
+}
+
 static int compact_range(plx_lattice *L, const uint32_t *keys, uint32_t mask, int total, int64_t begin, int64_t count,
                          bool csr, int kept, int *out_a, float *out_w, int *out_b, hipStream_t stream)
 {
@@ -173,7 +178,7 @@ int ensure_rows_splat(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t str
     PLX_TRY(ensure(L->rows_vid, (size_t)kept * 4));
     PLX_TRY(compact_range(L, L->csr_row.as<uint32_t>(), 0x7FFFFFFFu, (int)L->nnz, r->begin, r->count, true, kept,
                           r->row.as<int>(), r->w.as<float>(), L->rows_vid.as<int>(), stream));
-    rows_ptr_kernel<<<ceil_div((int64_t)m + 1, kBlock), kBlock, 0, stream>>>(L->rows_vid.as<int>(), kept, m, r->ptr.as<int>());
+    rows_ptr_launch(L->rows_vid.as<int>(), kept, m, r->ptr.as<int>(), stream);
     PLX_HIP_TRY(hipGetLastError());
     r->splat_ready = true;
     return PLX_OK;
@@ -325,31 +330,38 @@ static inline int rows_group_shift(int nch)
     return s;
 }
 
-int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t count, int vd, float *d_values,
-                           hipStream_t stream)
+const char *splat_rows_launch(const int *ptr, const int *row, const float *w, const float *d_src, int vd, int m, float *d_values,
+                              hipStream_t stream)
 {
-    plx_lattice::RowsRange *r = range_slot(L, begin, count);
-    PLX_TRY(ensure_rows_splat(L, r, stream));
-    const int m = (int)L->m, nch = values_stride(vd) / 4;
-    const int *ptr = r->ptr.as<int>(), *row = r->row.as<int>();
-    const float *w = r->w.as<float>();
+    const int nch = values_stride(vd) / 4;
     const bool vec = rows_vec_ok(d_src, vd);
     float4 *v4 = reinterpret_cast<float4 *>(d_values);
+    const char *kn_rows_splat;            // (named as the member the row-range splat keeps it in)
     if (vd == 1) {
-        L->kn_rows_splat = "rows_splat_v1_kernel";
+        kn_rows_splat = "rows_splat_v1_kernel";
         rows_splat_v1_kernel<<<ceil_div(m, kBlock), kBlock, 0, stream>>>(ptr, row, w, d_src, m, d_values);
     } else if (nch <= kRowsChunkMax) {
-        L->kn_rows_splat = "rows_splat_chunk_kernel";
+        kn_rows_splat = "rows_splat_chunk_kernel";
         const int shift = rows_group_shift(nch);
         const int grid = ceil_div((int64_t)m << shift, kBlock);
         if (vec) rows_splat_chunk_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v4);
         else rows_splat_chunk_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v4);
     } else {
-        L->kn_rows_splat = "rows_splat_wide_kernel";
+        kn_rows_splat = "rows_splat_wide_kernel";
         const int grid = ceil_div(m, kBlock / 64);
         if (vec) rows_splat_wide_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, m, v4);
         else rows_splat_wide_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, m, v4);
     }
+    return kn_rows_splat;
+}
+
+int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t count, int vd, float *d_values,
+                           hipStream_t stream)
+{
+    plx_lattice::RowsRange *r = range_slot(L, begin, count);
+    PLX_TRY(ensure_rows_splat(L, r, stream));
+    L->kn_rows_splat = splat_rows_launch(r->ptr.as<int>(), r->row.as<int>(), r->w.as<float>(), d_src, vd, (int)L->m, d_values,
+                                         stream);
     PLX_HIP_TRY(hipGetLastError());
     return PLX_OK;
 }

@@ -135,31 +135,38 @@ __global__ __launch_bounds__(kBlock) void rows64_slice_wide_kernel(const int *__
 }
 
 // ---- launch side ---------------------------------------------------------------------------------------------------
-int splat_rows_f64_impl(plx_lattice *L, const double *d_src, int64_t begin, int64_t count, int vd, double *d_values,
-                        hipStream_t stream)
+const char *splat_rows_f64_launch(const int *ptr, const int *row, const float *w, const double *d_src, int vd, int m,
+                                  double *d_values, hipStream_t stream)
 {
-    plx_lattice::RowsRange *r = range_slot(L, begin, count);
-    PLX_TRY(ensure_rows_splat(L, r, stream));
-    const int m = (int)L->m, nch = values_stride_f64(vd) / 2;
-    const int *ptr = r->ptr.as<int>(), *row = r->row.as<int>();
-    const float *w = r->w.as<float>();
+    const int nch = values_stride_f64(vd) / 2;
     const bool vec = f64_vec_ok(d_src, vd);
     double2 *v2 = reinterpret_cast<double2 *>(d_values);
+    const char *kn_rows64_splat;          // (named as the member the row-range splat keeps it in)
     if (vd == 1) {
-        L->kn_rows64_splat = "rows64_splat_v1_kernel";
+        kn_rows64_splat = "rows64_splat_v1_kernel";
         rows64_splat_v1_kernel<<<ceil_div(m, kBlock), kBlock, 0, stream>>>(ptr, row, w, d_src, m, d_values);
     } else if (nch <= kChunkGroupMax) {
-        L->kn_rows64_splat = "rows64_splat_chunk_kernel";
+        kn_rows64_splat = "rows64_splat_chunk_kernel";
         const int shift = chunk_group_shift(nch);
         const int grid = ceil_div((int64_t)m << shift, kBlock);
         if (vec) rows64_splat_chunk_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v2);
         else rows64_splat_chunk_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v2);
     } else {
-        L->kn_rows64_splat = "rows64_splat_wide_kernel";
+        kn_rows64_splat = "rows64_splat_wide_kernel";
         const int grid = ceil_div(m, kBlock / 64);
         if (vec) rows64_splat_wide_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, m, v2);
         else rows64_splat_wide_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, m, v2);
     }
+    return kn_rows64_splat;
+}
+
+int splat_rows_f64_impl(plx_lattice *L, const double *d_src, int64_t begin, int64_t count, int vd, double *d_values,
+                        hipStream_t stream)
+{
+    plx_lattice::RowsRange *r = range_slot(L, begin, count);
+    PLX_TRY(ensure_rows_splat(L, r, stream));
+    L->kn_rows64_splat = splat_rows_f64_launch(r->ptr.as<int>(), r->row.as<int>(), r->w.as<float>(), d_src, vd, (int)L->m,
+                                               d_values, stream);
     PLX_HIP_TRY(hipGetLastError());
     return PLX_OK;
 }

@@ -402,8 +402,8 @@ class LatticeSliceAt(Function):
 
     The slice is piecewise linear in x; the backward is its exact derivative inside the simplex locate chose
     (query_grad.slice_at_backward: plx_slice_at_dots + plx_locate_pullback), returned in the dtype of
-    x.  Once differentiable.  `mass` (locate's) carries no gradient.  `values` is a constant: its gradient is the adjoint
-    splat at the query points, which is not built, so a `values` that requires a gradient is refused.  x and values are
+    x.  Once differentiable.  `mass` (locate's) carries no gradient.  `values` is a constant here, and a `values` that requires a
+    gradient is refused: LatticeSliceAtValues differentiates it (the adjoint splat at the query points).  x and values are
     saved for the backward: changing either in place in between is an autograd error, not a wrong gradient."""
 
     @staticmethod
@@ -428,6 +428,68 @@ class LatticeSliceAt(Function):
             g = grad_out.to(values.dtype).contiguous()
             grad_x = query_grad.slice_at_backward(ctx.lat, values, ctx.query, g, vd=ctx.vd).to(x.dtype)
         return grad_x, None, None, None
+
+
+class LatticeSliceAtValues(Function):
+    """LatticeSliceAt with a gradient for `values` too: (out, mass) = locate + slice_at, and in the backward
+    grad_values = query_adjoint.slice_at_adjoint(grad_out) -- S*^T grad_out / (1 + 2^-d), one plan and one launch, no
+    atomics -- beside the grad_x of LatticeSliceAt where x requires it.  Once differentiable; `mass`
+    carries no gradient.  grad_values is [m, stride] like `values`, exact zeros in the stride padding."""
+
+    @staticmethod
+    def forward(ctx, x, values, lat, vd=None):
+        query = lat.locate(x.detach())
+        out = lat.slice_at(values.detach(), query, vd=vd)
+        ctx.lat, ctx.query, ctx.vd = lat, query, out.shape[1]
+        ctx.save_for_backward(x, values)
+        ctx.mark_non_differentiable(query.mass)
+        return out, query.mass
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_mass):
+        from . import query_adjoint, query_grad
+        x, values = ctx.saved_tensors
+        g = grad_out.to(values.dtype).contiguous()
+        grad_x = grad_values = None
+        if ctx.needs_input_grad[0]:
+            grad_x = query_grad.slice_at_backward(ctx.lat, values, ctx.query, g, vd=ctx.vd).to(x.dtype)
+        if ctx.needs_input_grad[1]:
+            grad_values = query_adjoint.slice_at_adjoint(ctx.lat, g, ctx.query)
+            if grad_values.shape[0] != values.shape[0]:       # a values buffer with spare rows: they were not read
+                grad_values = torch.cat([grad_values, grad_values.new_zeros(values.shape[0] - grad_values.shape[0],
+                                                                             grad_values.shape[1])])
+        return grad_x, grad_values, None, None
+
+
+class LatticeQueryProduct(Function):
+    """(K_q src, mass) for the built lattice `lat`, src [n, vd] and the points x [nq, d] (in the build's units):
+    Lattice.blurred + locate + slice_at.  Backward: grad_src = query_adjoint.apply_at_t(grad_out), the exact transpose of
+    the forward map (S_X blur_t S*^T / (1 + 2^-d)), and grad_x as in LatticeSliceAt from the blurred buffer the forward
+    kept.  One plan per backward.  Once differentiable; `mass` carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, lat, src, x):
+        values, vd = lat.blurred(src.detach())
+        query = lat.locate(x.detach())
+        out = lat.slice_at(values, query, vd=vd)
+        ctx.lat, ctx.query, ctx.vd, ctx.values = lat, query, vd, values
+        ctx.save_for_backward(x)
+        ctx.src_dtype = src.dtype
+        ctx.mark_non_differentiable(query.mass)
+        return out, query.mass
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_mass):
+        from . import query_adjoint, query_grad
+        (x,) = ctx.saved_tensors
+        g = grad_out.to(ctx.src_dtype).contiguous()
+        grad_src = query_adjoint.apply_at_t(ctx.lat, g, ctx.query) if ctx.needs_input_grad[1] else None
+        grad_x = None
+        if ctx.needs_input_grad[2]:
+            grad_x = query_grad.slice_at_backward(ctx.lat, ctx.values, ctx.query, g, vd=ctx.vd).to(x.dtype)
+        return None, grad_src, grad_x
 
 
 def rows_route(device_type, dtype, dim, hook, requires_grad, enabled=True, columns=None, min_columns=1, f64=False,
