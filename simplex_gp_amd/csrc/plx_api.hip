@@ -482,7 +482,7 @@ static int apply_common(plx_lattice *L, const float *d_src, int vd, float *d_out
     return slice_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, d_out, s, d_affine, d_src);
 }
 
-// ---- the rectangular product: splat / slice by row range (kernels and tables: plx_rows.hip) ----------------------------
+// ---- the rectangular product: splat / slice by row range (kernels: plx_rows_kernels.h; tables: plx_rows.hip) ----------
 
 // The two checks the rows calls and the fp64 calls share.  A range of caller rows: non-empty, inside [0, n).
 static int check_range(const plx_lattice *L, int64_t begin, int64_t count, const char *who)
@@ -532,7 +532,7 @@ int plx_splat_rows(plx_lattice *L, const float *d_src, int64_t row_begin, int64_
     PLX_TRY(check_rows(L, d_src, d_values, vd, row_begin, row_count, "plx_splat_rows"));
     PLX_TRY(check_values_aligned(d_values, vd, "plx_splat_rows"));
     DeviceGuard g(L->device);
-    return splat_rows_impl(L, d_src, row_begin, row_count, vd, d_values, (hipStream_t)stream);
+    return splat_rows_impl<float>(L, d_src, row_begin, row_count, vd, d_values, (hipStream_t)stream);
 }
 
 int plx_slice_rows(plx_lattice *L, const float *d_values, int vd, int64_t row_begin, int64_t row_count, float *d_out,
@@ -542,7 +542,7 @@ int plx_slice_rows(plx_lattice *L, const float *d_values, int vd, int64_t row_be
     PLX_TRY(check_rows(L, d_values, d_out, vd, row_begin, row_count, "plx_slice_rows"));
     PLX_TRY(check_values_aligned(d_values, vd, "plx_slice_rows"));
     DeviceGuard g(L->device);
-    return slice_rows_impl(L, d_values, vd, row_begin, row_count, d_out, (hipStream_t)stream);
+    return slice_rows_impl<float>(L, d_values, vd, row_begin, row_count, d_out, (hipStream_t)stream);
 }
 
 int plx_apply_rows(plx_lattice *L, const float *d_src, int64_t src_begin, int64_t src_count, int vd, float *d_out,
@@ -555,10 +555,10 @@ int plx_apply_rows(plx_lattice *L, const float *d_src, int64_t src_begin, int64_
     hipStream_t s = (hipStream_t)stream;
     PLX_TRY(ensure(L->val_a, (size_t)L->m * values_stride(vd) * 4));
     PLX_TRY(ensure(L->val_b, (size_t)L->m * values_stride(vd) * 4));
-    PLX_TRY(splat_rows_impl(L, d_src, src_begin, src_count, vd, L->val_a.as<float>(), s));
+    PLX_TRY(splat_rows_impl<float>(L, d_src, src_begin, src_count, vd, L->val_a.as<float>(), s));
     int in_b = 0;
     PLX_TRY(blur_impl(L, L->val_a.as<float>(), L->val_b.as<float>(), vd, &in_b, s));
-    return slice_rows_impl(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, out_begin, out_count, d_out, s);
+    return slice_rows_impl<float>(L, in_b ? L->val_b.as<float>() : L->val_a.as<float>(), vd, out_begin, out_count, d_out, s);
 }
 
 int plx_last_rows_kernels(const plx_lattice *L, char *buf, int cap)
@@ -1251,7 +1251,7 @@ int plx_last_splat_at_kernels(const plx_lattice *L, char *buf, int cap)
     return PLX_OK;
 }
 
-// ---- the float64 rectangular product (kernels: plx_rows_f64.hip; tables: plx_rows.hip; blur: plx_f64.hip) --------------
+// ---- the float64 rectangular product (kernels: plx_rows_kernels.h; tables: plx_rows.hip; blur: plx_f64.hip) ------------
 
 // check_rows and check_f64 in one: the checks of both, each once.
 static int check_rows_f64(const plx_lattice *L, const void *a, const void *b, int vd, int64_t begin, int64_t count,
@@ -1271,7 +1271,7 @@ int plx_splat_rows_f64(plx_lattice *L, const double *d_src, int64_t row_begin, i
     PLX_TRY(check_rows_f64(L, d_src, d_values, vd, row_begin, row_count, "plx_splat_rows_f64"));
     PLX_TRY(check_values_aligned(d_values, vd, "plx_splat_rows_f64"));
     DeviceGuard g(L->device);
-    return splat_rows_f64_impl(L, d_src, row_begin, row_count, vd, d_values, (hipStream_t)stream);
+    return splat_rows_impl<double>(L, d_src, row_begin, row_count, vd, d_values, (hipStream_t)stream);
 }
 
 int plx_slice_rows_f64(plx_lattice *L, const double *d_values, int vd, int64_t row_begin, int64_t row_count, double *d_out,
@@ -1281,7 +1281,7 @@ int plx_slice_rows_f64(plx_lattice *L, const double *d_values, int vd, int64_t r
     PLX_TRY(check_rows_f64(L, d_values, d_out, vd, row_begin, row_count, "plx_slice_rows_f64"));
     PLX_TRY(check_values_aligned(d_values, vd, "plx_slice_rows_f64"));
     DeviceGuard g(L->device);
-    return slice_rows_f64_impl(L, d_values, vd, row_begin, row_count, d_out, (hipStream_t)stream);
+    return slice_rows_impl<double>(L, d_values, vd, row_begin, row_count, d_out, (hipStream_t)stream);
 }
 
 int plx_apply_rows_f64(plx_lattice *L, const double *d_src, int64_t src_begin, int64_t src_count, int vd, double *d_out,
@@ -1294,10 +1294,10 @@ int plx_apply_rows_f64(plx_lattice *L, const double *d_src, int64_t src_begin, i
     hipStream_t s = (hipStream_t)stream;
     PLX_TRY(ensure(L->val64_a, (size_t)L->m * values_stride_f64(vd) * 8));      // the workspace of plx_apply_f64
     PLX_TRY(ensure(L->val64_b, (size_t)L->m * values_stride_f64(vd) * 8));
-    PLX_TRY(splat_rows_f64_impl(L, d_src, src_begin, src_count, vd, L->val64_a.as<double>(), s));
+    PLX_TRY(splat_rows_impl<double>(L, d_src, src_begin, src_count, vd, L->val64_a.as<double>(), s));
     int in_b = 0;
     PLX_TRY(blur_f64_impl(L, L->val64_a.as<double>(), L->val64_b.as<double>(), vd, &in_b, s));
-    return slice_rows_f64_impl(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, out_begin, out_count, d_out, s);
+    return slice_rows_impl<double>(L, in_b ? L->val64_b.as<double>() : L->val64_a.as<double>(), vd, out_begin, out_count, d_out, s);
 }
 
 int plx_last_rows_f64_kernels(const plx_lattice *L, char *buf, int cap)

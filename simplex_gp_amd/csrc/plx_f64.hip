@@ -9,7 +9,7 @@
 // Value rows: vd = 1 -> one double per vertex; vd > 1 -> vdp = vd rounded up to 2 doubles, i.e. nch = vdp / 2 double2
 // "chunks", one aligned 16-byte access per lane.  Rows of d_src / d_out are in the caller's order, always.
 //
-// Kernels (256-thread workgroups, wave64), the three shapes of plx_rows.hip per gather stage:
+// Kernels (256-thread workgroups, wave64), the three shapes of plx_rows_kernels.h per gather stage:
 //   f64_splat_v1_kernel     vd = 1: one thread per vertex adds up its corners, in ensure_csr's order;
 //   f64_splat_chunk_kernel  1..64 chunks per row: a group of G = 2^k >= chunks lanes per vertex, one lane per chunk;
 //   f64_splat_wide_kernel   more than 64 chunks: one wave per vertex, its lanes stride over the chunks;
@@ -127,7 +127,9 @@ __global__ __launch_bounds__(kBlock) void f64_blur_chunk_kernel(const double2 *_
 }
 
 // ---- slice ---------------------------------------------------------------------------------------------------------
-// D1 > 0: d + 1 compiled in (all index / weight loads, then all gathers, then the ordered sum); 0: the run-time form
+// D1 > 0: d + 1 compiled in (all index loads, then all gathers, then the ordered sum); 0: the run-time form.  The chunk sum
+// is f64_filtered_chunk (plx_kernels.h), shared with the row-range and the query slices; the vd = 1 sum is f64_filtered_v1
+// there, written out here because the call moved two instructions of the run-time loop.
 template <int D1>
 __global__ __launch_bounds__(kBlock) void f64_slice_v1_kernel(const uint32_t *__restrict__ perm, const int *__restrict__ evid,
                                                               const float *__restrict__ ew, int n, int d1,
@@ -163,21 +165,7 @@ __global__ __launch_bounds__(kBlock) void f64_slice_chunk_kernel(const uint32_t 
     const int ch = (int)(t & ((1 << shift) - 1));
     if (p64 >= n || ch >= nch) return;
     const int p = (int)p64;
-    double2 acc;
-    if constexpr (D1 > 0) {
-        int v[D1];
-        double2 g[D1];
-#pragma unroll
-        for (int r = 0; r < D1; ++r) v[r] = evid[(size_t)r * n + p];
-#pragma unroll
-        for (int r = 0; r < D1; ++r) g[r] = values[(size_t)v[r] * nch + ch];
-        acc = VecOps<double2>::zero();
-#pragma unroll
-        for (int r = 0; r < D1; ++r) VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], g[r]);
-        acc = make_double2(acc.x / denom, acc.y / denom);
-    } else {
-        acc = f64_point_sum(evid, ew, n, p, d1, values, nch, ch, denom);
-    }
+    const double2 acc = f64_filtered_chunk<D1>(evid, ew, n, p, d1, values, nch, ch, denom);
     f64_store_chunk<VEC>(out, (size_t)perm[p], vd, ch, acc);
 }
 

@@ -402,11 +402,12 @@ void blur_axis_general(plx_lattice *L, const float *cur, float *nxt, int axis, i
 int blur_t_impl(plx_lattice *L, float *d_values, float *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);
 int blur_sym_planes(const plx_lattice *L);
 int blur_sym_impl(plx_lattice *L, float *d_values, float *const d_work[3], int vd, float **d_result, hipStream_t stream);
-// plx_rows.hip: splat / slice restricted to the caller's rows [begin, begin + count) (arguments checked by the entry points)
-int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t count, int vd, float *d_values,
-                    hipStream_t stream);
-int slice_rows_impl(plx_lattice *L, const float *d_values, int vd, int64_t begin, int64_t count, float *d_out,
-                    hipStream_t stream);
+// plx_rows_kernels.h, instantiated by plx_rows.hip (float) and plx_rows_f64.hip (double): splat / slice restricted to the
+// caller's rows [begin, begin + count) (arguments checked by the entry points)
+template <typename T>
+int splat_rows_impl(plx_lattice *L, const T *d_src, int64_t begin, int64_t count, int vd, T *d_values, hipStream_t stream);
+template <typename T>
+int slice_rows_impl(plx_lattice *L, const T *d_values, int vd, int64_t begin, int64_t count, T *d_out, hipStream_t stream);
 // ... and the range tables, which hold no values and serve both precisions: the slot of a range (the one that holds it,
 // else an empty one, else the least recently used) and its splat / slice side, built on first use
 plx_lattice::RowsRange *range_slot(plx_lattice *L, int64_t begin, int64_t count);
@@ -417,21 +418,15 @@ int ensure_rows_slice(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t str
 // the sums of w[j] * src[row[j]] over [ptr[v], ptr[v + 1]) in one launch of the family the row width picks, whose name
 // is returned (the caller asks hipGetLastError)
 void rows_ptr_launch(const int *vid, int kept, int m, int *ptr, hipStream_t stream);
-const char *splat_rows_launch(const int *ptr, const int *row, const float *w, const float *d_src, int vd, int m, float *d_values,
+template <typename T>
+const char *splat_rows_launch(const int *ptr, const int *row, const float *w, const T *d_src, int vd, int m, T *d_values,
                               hipStream_t stream);
-const char *splat_rows_f64_launch(const int *ptr, const int *row, const float *w, const double *d_src, int vd, int m,
-                                  double *d_values, hipStream_t stream);
 // plx_query_adjoint.hip: the plan of a located query (its found corners sorted by vertex, laid out in the caller's buffer)
 // and the splat over it (arguments checked by the entry points).  Launches only.
 int64_t query_plan_bytes(int64_t m, int d, int64_t nq);
 int query_plan_impl(plx_lattice *L, const int32_t *d_vid, const float *d_w, int64_t nq, void *d_plan, hipStream_t stream);
 template <typename T>
 int splat_at_impl(plx_lattice *L, const void *d_plan, const T *d_g, int vd, int64_t nq, T *d_values, hipStream_t stream);
-// plx_rows_f64.hip: the same two stages on buffers of doubles, over the same tables
-int splat_rows_f64_impl(plx_lattice *L, const double *d_src, int64_t begin, int64_t count, int vd, double *d_values,
-                        hipStream_t stream);
-int slice_rows_f64_impl(plx_lattice *L, const double *d_values, int vd, int64_t begin, int64_t count, double *d_out,
-                        hipStream_t stream);
 // plx_f64.hip: the three stages in float64 on caller buffers of doubles (arguments checked by the entry points)
 int splat_f64_impl(plx_lattice *L, const double *d_src, int vd, double *d_values, hipStream_t stream);
 int blur_f64_impl(plx_lattice *L, double *d_values, double *d_scratch, int vd, int *result_in_scratch, hipStream_t stream);

@@ -1,6 +1,6 @@
 // plx_kernels.h -- device helpers and launch-side switches shared by the per-MVM kernel files (plx_splat.hip,
-// plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_rows.hip, plx_f64.hip,
-// plx_rows_f64.hip, plx_backward_f64.hip, through plx_rows_backward_kernels.h plx_rows_backward.hip and
+// plx_blur.hip, plx_slice.hip, plx_block.hip, plx_first.hip, plx_onehot.hip, plx_f64.hip, plx_backward_f64.hip,
+// through plx_rows_kernels.h plx_rows.hip and plx_rows_f64.hip, through plx_rows_backward_kernels.h plx_rows_backward.hip and
 // plx_rows_backward_f64.hip, through plx_sym_kernels.h plx_sym.hip and plx_sym_f64.hip, through plx_diag_kernels.h
 // plx_diag.hip and plx_diag_f64.hip, and through plx_query_kernels.h plx_query.hip and plx_query_f64.hip).  Not part of
 // the C ABI.
@@ -25,6 +25,7 @@
 
 #include "plx_internal.h"
 
+#include <math.h>
 #include <type_traits>
 
 namespace plx {
@@ -91,8 +92,8 @@ template <> struct VecOps<double2> {
     static __device__ __forceinline__ void fma(double2 &acc, double s, double2 x) { acc.x += s * x.x; acc.y += s * x.y; }
 };
 
-// ---- the float64 gathers (plx_f64.hip, plx_rows_f64.hip): the pieces both files form their sums from, so that the same
-// terms in the same order give the same bits in both ----
+// ---- the float64 gathers (plx_f64.hip and, through Gather<double> below, the row-range product and the queries): the
+// pieces all of them form their sums from, so that the same terms in the same order give the same bits in each ----
 // one chunk of a caller row: a 16-byte access where the rows are whole aligned chunks, else per double with the tail guarded
 template <bool VEC>
 __device__ __forceinline__ double2 f64_load_chunk(const double *__restrict__ src, size_t row, int vd, int ch)
@@ -144,6 +145,64 @@ __device__ __forceinline__ double2 f64_point_sum(const int *__restrict__ evid, c
         }
     }
     return make_double2(acc.x / denom, acc.y / denom);
+}
+
+// chunk ch of the filtered row of point p, the sum of the float64 chunk slices (f64_slice_chunk_kernel, the row-range and the
+// query ones).  D1 > 0: d + 1 compiled in -- all ids, then all gathers, then the ordered sum with each weight converted where
+// it is used, then ONE division; 0: the run-time form.  (filtered_chunk64 below reads its weights first: other registers.
+// And the gather is spelled per SKIP: assigned from a conditional it is one 16-byte load, assigned directly two of 8.)
+template <int D1, bool SKIP = false>
+__device__ __forceinline__ double2 f64_filtered_chunk(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
+                                                      int d1, const double2 *__restrict__ values, int nch, int ch, double denom)
+{
+    if constexpr (D1 > 0) {
+        int v[D1];
+        double2 g[D1];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) v[r] = evid[(size_t)r * n + p];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) {
+            if constexpr (SKIP) g[r] = v[r] >= 0 ? values[(size_t)v[r] * nch + ch] : VecOps<double2>::zero();
+            else g[r] = values[(size_t)v[r] * nch + ch];
+        }
+        double2 acc = VecOps<double2>::zero();
+#pragma unroll
+        for (int r = 0; r < D1; ++r)
+            if (!SKIP || v[r] >= 0) VecOps<double2>::fma(acc, (double)ew[(size_t)r * n + p], g[r]);
+        return make_double2(acc.x / denom, acc.y / denom);
+    } else {
+        return f64_point_sum<SKIP>(evid, ew, n, p, d1, values, nch, ch, denom);
+    }
+}
+
+// ... and the vd = 1 sum of the same slices, in the same two forms
+template <int D1, bool SKIP = false>
+__device__ __forceinline__ double f64_filtered_v1(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p, int d1,
+                                                  const double *__restrict__ values, double denom)
+{
+    double acc = 0.0;
+    if constexpr (D1 > 0) {
+        int v[D1];
+        double g[D1];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) v[r] = evid[(size_t)r * n + p];
+#pragma unroll
+        for (int r = 0; r < D1; ++r) g[r] = !SKIP || v[r] >= 0 ? values[v[r]] : 0.0;
+#pragma unroll
+        for (int r = 0; r < D1; ++r)
+            if (!SKIP || v[r] >= 0) acc += (double)ew[(size_t)r * n + p] * g[r];
+    } else {
+        if constexpr (SKIP) {
+            for (int r = 0; r < d1; ++r) {
+                const int v = evid[(size_t)r * n + p];
+                if (v < 0) continue;
+                acc += (double)ew[(size_t)r * n + p] * values[v];
+            }
+        } else {
+            for (int r = 0; r < d1; ++r) acc += (double)ew[(size_t)r * n + p] * values[evid[(size_t)r * n + p]];
+        }
+    }
+    return acc / denom;
 }
 
 // ---- the float64 position gradients (plx_backward_f64.hip, plx_rows_backward_f64.hip): the stack formed inside the splat
@@ -226,7 +285,7 @@ __device__ __forceinline__ double2 filtered_chunk64(const Corners64<D1> &c, cons
     }
 }
 
-// ---- the fp32 row-range slices (plx_rows.hip, plx_rows_backward.hip): the sums both files form a filtered chunk from, so
+// ---- the fp32 row-range slices (Gather<float> below, plx_rows_backward.hip): the sums both form a filtered chunk from, so
 // that the same terms in the same order give the same bits in both ----
 // acc += (w g) rden per element: the product w g rounded, then ONE fused multiply-add.  Written with the rounding spelled out:
 // left to -ffp-contract=fast, `acc += w * g * rden` compiled to this in every kernel but the unaligned chunk slice, whose
@@ -303,7 +362,7 @@ static inline int chunk_group_shift(int nch)
     return s;
 }
 
-// The gather slices of plx_rows.hip, plx_f64.hip and plx_rows_f64.hip have d + 1 compiled in up to kGatherMaxD1:
+// The gather slices of plx_rows_kernels.h, plx_query_kernels.h and plx_f64.hip have d + 1 compiled in up to kGatherMaxD1:
 // f(std::integral_constant<int, D1>) with D1 = d1 for 2..20, else 0 (the run-time form).
 constexpr int kGatherMaxD1 = 20;
 template <class F> static inline void dispatch_d1(int d1, F &&f)
@@ -317,5 +376,131 @@ template <class F> static inline void dispatch_d1(int d1, F &&f)
     default: f(std::integral_constant<int, 0>{}); break;
     }
 }
+
+// ---- what the gathers of a caller type T differ in (the row-range product, plx_rows_kernels.h, and the slices at located
+// queries, plx_query_kernels.h): the 16-byte chunk Vec, the normalisation Den, one chunk of a caller row (load / store: a
+// 16-byte access where the rows are whole aligned chunks, else per element with the tail guarded), the sum over the corners
+// of a vertex (vertex_sum) and the three sums over the corners of a point: v1 (vd = 1), chunk (d + 1 compiled in up to
+// kGatherMaxD1) and wide.  Every sum is that type's own text: one body for both would change roundings or registers in one
+// of them.  SKIP = false, the row-range product: every id is a vertex.  SKIP = true, the queries: (evid, ew) are the
+// located (vid, w) with nq for n, and a corner whose id is negative is absent.  It is skipped, never multiplied by zero:
+// the vertex array may hold non-finite values elsewhere.  With every corner present both give the same terms in the same
+// order, hence the same bits.
+template <typename T> struct Gather;
+
+template <> struct Gather<float> {
+    using Vec = float4;
+    using Den = float;                        // the rounded reciprocal of 1 + 2^-d: every term is multiplied (rows_term)
+    static constexpr int kPer = 4;            // elements per chunk
+    static constexpr bool kV1Compiled = false;      // v1 reads its corners in a run-time loop
+    static int stride(int vd) { return values_stride(vd); }
+    static Den den(const plx_lattice *L) { return 1.0f / L->slice_denom; }
+    static bool vec_ok(const void *p, int vd) { return (vd & 3) == 0 && ((uintptr_t)p & 15) == 0; }
+    template <bool VEC> static __device__ __forceinline__ float4 load(const float *__restrict__ src, size_t row, int vd, int ch)
+    {
+        const float *p = src + row * vd + 4 * ch;
+        if constexpr (VEC) return *reinterpret_cast<const float4 *>(p);
+        const int left = vd - 4 * ch;
+        float4 x = f4_zero();
+        x.x = p[0];
+        if (left > 1) x.y = p[1];
+        if (left > 2) x.z = p[2];
+        if (left > 3) x.w = p[3];
+        return x;
+    }
+    template <bool VEC> static __device__ __forceinline__ void store(float *__restrict__ out, size_t row, int vd, int ch, float4 a)
+    {
+        float *o = out + row * vd + 4 * ch;
+        if constexpr (VEC) { *reinterpret_cast<float4 *>(o) = a; return; }
+        const int left = vd - 4 * ch;
+        o[0] = a.x;
+        if (left > 1) o[1] = a.y;
+        if (left > 2) o[2] = a.z;
+        if (left > 3) o[3] = a.w;
+    }
+    template <bool VEC>
+    static __device__ __forceinline__ float4 vertex_sum(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
+                                                        const float *__restrict__ src, int vd, int ch)
+    {
+        float4 acc = f4_zero();
+        for (int j = j0; j < j1; ++j) {
+            const float wj = w[j];
+            const float4 x = load<VEC>(src, (size_t)row[j], vd, ch);
+            acc.x += wj * x.x; acc.y += wj * x.y; acc.z += wj * x.z; acc.w += wj * x.w;
+        }
+        return acc;
+    }
+    // the run-time loop (D1 is not used), each form as its kernel had it
+    template <int D1, bool SKIP>
+    static __device__ __forceinline__ float v1(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p, int d1,
+                                               const float *__restrict__ values, float rden)
+    {
+        float acc = 0.f;
+        if constexpr (SKIP) {
+            for (int r = 0; r < d1; ++r) {
+                const int v = evid[(size_t)r * n + p];
+                if (v < 0) continue;
+                acc += ew[(size_t)r * n + p] * values[v] * rden;
+            }
+        } else {
+            for (int r = 0; r < d1; ++r) acc += ew[(size_t)r * n + p] * values[evid[(size_t)r * n + p]] * rden;
+        }
+        return acc;
+    }
+    template <int D1, bool SKIP>
+    static __device__ __forceinline__ float4 chunk(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p, int d1,
+                                                   const float4 *__restrict__ values, int nch, int ch, float rden)
+    {
+        return rows_filtered_chunk<D1, SKIP>(evid, ew, n, p, d1, values, nch, ch, rden);
+    }
+    template <bool SKIP>
+    static __device__ __forceinline__ float4 wide(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p, int d1,
+                                                  const float4 *__restrict__ values, int nch, int ch, float rden)
+    {
+        return rows_point_sum<SKIP>(evid, ew, n, p, d1, values, nch, ch, rden);
+    }
+};
+
+template <> struct Gather<double> {
+    using Vec = double2;
+    using Den = double;                       // 1 + 2^-d itself: the double slices divide their sum once
+    static constexpr int kPer = 2;
+    static constexpr bool kV1Compiled = true;       // v1 has d + 1 compiled in
+    static int stride(int vd) { return values_stride_f64(vd); }
+    static Den den(const plx_lattice *L) { return 1.0 + ldexp(1.0, -L->d); }
+    static bool vec_ok(const void *p, int vd) { return f64_vec_ok(p, vd); }
+    template <bool VEC> static __device__ __forceinline__ double2 load(const double *__restrict__ src, size_t row, int vd, int ch)
+    {
+        return f64_load_chunk<VEC>(src, row, vd, ch);
+    }
+    template <bool VEC> static __device__ __forceinline__ void store(double *__restrict__ out, size_t row, int vd, int ch, double2 a)
+    {
+        f64_store_chunk<VEC>(out, row, vd, ch, a);
+    }
+    template <bool VEC>
+    static __device__ __forceinline__ double2 vertex_sum(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
+                                                         const double *__restrict__ src, int vd, int ch)
+    {
+        return f64_vertex_sum<VEC>(row, w, j0, j1, src, vd, ch);
+    }
+    template <int D1, bool SKIP>
+    static __device__ __forceinline__ double v1(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p, int d1,
+                                                const double *__restrict__ values, double denom)
+    {
+        return f64_filtered_v1<D1, SKIP>(evid, ew, n, p, d1, values, denom);
+    }
+    template <int D1, bool SKIP>
+    static __device__ __forceinline__ double2 chunk(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
+                                                    int d1, const double2 *__restrict__ values, int nch, int ch, double denom)
+    {
+        return f64_filtered_chunk<D1, SKIP>(evid, ew, n, p, d1, values, nch, ch, denom);
+    }
+    template <bool SKIP>
+    static __device__ __forceinline__ double2 wide(const int *__restrict__ evid, const float *__restrict__ ew, int n, int p,
+                                                   int d1, const double2 *__restrict__ values, int nch, int ch, double denom)
+    {
+        return f64_point_sum<SKIP>(evid, ew, n, p, d1, values, nch, ch, denom);
+    }
+};
 
 }  // namespace plx

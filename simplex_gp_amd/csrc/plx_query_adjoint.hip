@@ -10,8 +10,8 @@
 // w[j] = d_w[pair], and ptr[u] = the first sorted position whose key is >= u, u = 0..m -- the tables of a row range
 // (plx_rows.hip), with the queries as the rows; ptr[m] is the number of corners found.  Inside a vertex the corners stand
 // in ascending pair index (the sort is stable): that IS the summation order, so two plans of one query give the same bits.
-// The SPLAT, one launch of the row-range splat's own kernels over those tables (splat_rows_launch /
-// splat_rows_f64_launch): every vertex row is written by exactly one thread per chunk, zeros where no query corner lands,
+// The SPLAT, one launch of the row-range splat's own kernels over those tables (splat_rows_launch<T>,
+// plx_rows_kernels.h): every vertex row is written by exactly one thread per chunk, zeros where no query corner lands,
 // no atomics, no zero-fill pass.
 //
 // Everything lives in the caller's plan buffer, laid out by plan_layout from (m, d, nq) alone; no buffer of the lattice is
@@ -100,8 +100,7 @@ int splat_at_impl(plx_lattice *L, const void *d_plan, const T *d_g, int vd, int6
     const char *base = static_cast<const char *>(d_plan);
     const int *ptr = reinterpret_cast<const int *>(base + o.ptr), *row = reinterpret_cast<const int *>(base + o.row);
     const float *w = reinterpret_cast<const float *>(base + o.w);
-    if constexpr (sizeof(T) == 8) L->kn_splat_at = splat_rows_f64_launch(ptr, row, w, d_g, vd, (int)L->m, d_values, stream);
-    else L->kn_splat_at = splat_rows_launch(ptr, row, w, d_g, vd, (int)L->m, d_values, stream);
+    L->kn_splat_at = splat_rows_launch<T>(ptr, row, w, d_g, vd, (int)L->m, d_values, stream);
     PLX_HIP_TRY(hipGetLastError());
     return PLX_OK;
 }

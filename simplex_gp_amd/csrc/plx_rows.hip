@@ -1,6 +1,7 @@
 // plx_rows.hip -- the rectangular product K[out rows, src rows] v: splat and slice restricted to a range of the caller's
 // rows (plx_splat_rows / plx_slice_rows / plx_apply_rows, include/plx.h; the entry points and their argument checks are in
-// plx_api.hip).  The blur in the middle is plx_blur's.
+// plx_api.hip).  Here: the tables of a row range, which have no scalar type and serve both precisions, and the fp32
+// product, plx_rows_kernels.h with T = float -- the splat and slice kernels and their launch side are there.
 //
 // Per range [begin, begin + count) of caller rows the lattice keeps (RowsRange, plx_internal.h), built by the first call
 // that needs them and dropped by the next build:
@@ -10,16 +11,8 @@
 //   slice side  the lattice positions of those rows, ascending (a stable compaction of the point permutation), each with
 //               its row - begin.
 // Both sizes are known on the host (count (d + 1) and count), so building them reads nothing back.
-//
-// Kernels (256-thread workgroups, wave64; value rows are whole 16-byte chunks, plx_kernels.h):
-//   rows_splat_v1_kernel     vd = 1: one thread per vertex adds up its corners, in order;
-//   rows_splat_chunk_kernel  1..64 chunks per row: a group of G = 2^k >= chunks lanes per vertex, one lane per chunk;
-//   rows_splat_wide_kernel   more than 64 chunks: one wave per vertex, its lanes stride over the chunks;
-//   rows_slice_v1_kernel / rows_slice_chunk_kernel / rows_slice_wide_kernel: the same three shapes per output point.
-// Every vertex row is written by exactly one thread per chunk (zero where the range has no corner there): no atomics, no
-// zero-fill pass, bitwise reproducible.  Why the gates sit at 1 and 64 chunks: DESIGN.md section 13.
 
-#include "plx_kernels.h"
+#include "plx_rows_kernels.h"
 
 namespace plx {
 
@@ -196,225 +189,20 @@ int ensure_rows_slice(plx_lattice *L, plx_lattice::RowsRange *r, hipStream_t str
     return PLX_OK;
 }
 
-// ---- splat ---------------------------------------------------------------------------------------------------------
-// one chunk of a source row: a 16-byte load where the rows are whole aligned chunks, else per float with the tail guarded
-template <bool VEC>
-__device__ __forceinline__ float4 rows_load_chunk(const float *__restrict__ src, size_t row, int vd, int ch)
-{
-    const float *p = src + row * vd + 4 * ch;
-    if constexpr (VEC) return *reinterpret_cast<const float4 *>(p);
-    const int left = vd - 4 * ch;
-    float4 x = f4_zero();
-    x.x = p[0];
-    if (left > 1) x.y = p[1];
-    if (left > 2) x.z = p[2];
-    if (left > 3) x.w = p[3];
-    return x;
-}
+// ---- the fp32 product: plx_rows_kernels.h with T = float -----------------------------------------------------------
+template <> struct Rows<float> {
+    static constexpr const char *plx_lattice::*kSplatField = &plx_lattice::kn_rows_splat;
+    static constexpr const char *plx_lattice::*kSliceField = &plx_lattice::kn_rows_slice;
+    static constexpr const char *kSplatV1 = "rows_splat_v1_kernel";
+    static constexpr const char *kSplatChunk = "rows_splat_chunk_kernel";
+    static constexpr const char *kSplatWide = "rows_splat_wide_kernel";
+    static constexpr const char *kSliceV1 = "rows_slice_v1_kernel";
+    static constexpr const char *kSliceChunk = "rows_slice_chunk_kernel";
+    static constexpr const char *kSliceWide = "rows_slice_wide_kernel";
+};
 
-template <bool VEC>
-__device__ __forceinline__ void rows_store_chunk(float *__restrict__ out, size_t row, int vd, int ch, float4 a)
-{
-    float *o = out + row * vd + 4 * ch;
-    if constexpr (VEC) { *reinterpret_cast<float4 *>(o) = a; return; }
-    const int left = vd - 4 * ch;
-    o[0] = a.x;
-    if (left > 1) o[1] = a.y;
-    if (left > 2) o[2] = a.z;
-    if (left > 3) o[3] = a.w;
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 rows_vertex_sum(const int *__restrict__ row, const float *__restrict__ w, int j0, int j1,
-                                                  const float *__restrict__ src, int vd, int ch)
-{
-    float4 acc = f4_zero();
-    for (int j = j0; j < j1; ++j) {
-        const float wj = w[j];
-        const float4 x = rows_load_chunk<VEC>(src, (size_t)row[j], vd, ch);
-        acc.x += wj * x.x; acc.y += wj * x.y; acc.z += wj * x.z; acc.w += wj * x.w;
-    }
-    return acc;
-}
-
-__global__ __launch_bounds__(kBlock) void rows_splat_v1_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
-                                                               const float *__restrict__ w, const float *__restrict__ src,
-                                                               int m, float *__restrict__ values)
-{
-    const int v = blockIdx.x * kBlock + threadIdx.x;
-    if (v >= m) return;
-    float acc = 0.f;
-    for (int j = ptr[v], j1 = ptr[v + 1]; j < j1; ++j) acc += w[j] * src[row[j]];
-    values[v] = acc;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void rows_splat_chunk_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
-                                                                  const float *__restrict__ w, const float *__restrict__ src,
-                                                                  int vd, int nch, int shift, int m,
-                                                                  float4 *__restrict__ values)
-{
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t v = t >> shift;
-    const int ch = (int)(t & ((1 << shift) - 1));
-    if (v >= m || ch >= nch) return;
-    values[(size_t)v * nch + ch] = rows_vertex_sum<VEC>(row, w, ptr[v], ptr[v + 1], src, vd, ch);
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void rows_splat_wide_kernel(const int *__restrict__ ptr, const int *__restrict__ row,
-                                                                 const float *__restrict__ w, const float *__restrict__ src,
-                                                                 int vd, int nch, int m, float4 *__restrict__ values)
-{
-    const int64_t v = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (v >= m) return;
-    const int j0 = ptr[v], j1 = ptr[v + 1];
-    for (int ch = threadIdx.x & 63; ch < nch; ch += 64)
-        values[(size_t)v * nch + ch] = rows_vertex_sum<VEC>(row, w, j0, j1, src, vd, ch);
-}
-
-// ---- slice ---------------------------------------------------------------------------------------------------------
-// (rows_point_sum and rows_filtered_chunk, the sums of a filtered chunk: plx_kernels.h, shared with the fp32 trait of
-// plx_rows_backward_kernels.h in plx_rows_backward.hip)
-__global__ __launch_bounds__(kBlock) void rows_slice_v1_kernel(const int *__restrict__ pos, const int *__restrict__ prow,
-                                                               const int *__restrict__ evid, const float *__restrict__ ew,
-                                                               int n, int d1, int count, const float *__restrict__ values,
-                                                               float rden, float *__restrict__ out)
-{
-    const int j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= count) return;
-    const int p = pos[j];
-    float acc = 0.f;
-    for (int r = 0; r < d1; ++r) acc += ew[(size_t)r * n + p] * values[evid[(size_t)r * n + p]] * rden;
-    out[prow[j]] = acc;
-}
-
-// D1 > 0: d + 1 compiled in (all index / weight loads, then all gathers, then the ordered sum); 0: the run-time form
-template <bool VEC, int D1>
-__global__ __launch_bounds__(kBlock) void rows_slice_chunk_kernel(const int *__restrict__ pos, const int *__restrict__ prow,
-                                                                  const int *__restrict__ evid, const float *__restrict__ ew,
-                                                                  int n, int d1, int count,
-                                                                  const float4 *__restrict__ values, int vd, int nch,
-                                                                  int shift, float rden, float *__restrict__ out)
-{
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t j = t >> shift;
-    const int ch = (int)(t & ((1 << shift) - 1));
-    if (j >= count || ch >= nch) return;
-    const float4 acc = rows_filtered_chunk<D1>(evid, ew, n, pos[j], d1, values, nch, ch, rden);
-    rows_store_chunk<VEC>(out, (size_t)prow[j], vd, ch, acc);
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void rows_slice_wide_kernel(const int *__restrict__ pos, const int *__restrict__ prow,
-                                                                 const int *__restrict__ evid, const float *__restrict__ ew,
-                                                                 int n, int d1, int count, const float4 *__restrict__ values,
-                                                                 int vd, int nch, float rden, float *__restrict__ out)
-{
-    const int64_t j = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (j >= count) return;
-    const int p = pos[j];
-    const size_t row = (size_t)prow[j];
-    for (int ch = threadIdx.x & 63; ch < nch; ch += 64)
-        rows_store_chunk<VEC>(out, row, vd, ch, rows_point_sum(evid, ew, n, p, d1, values, nch, ch, rden));
-}
-
-// ---- launch side ---------------------------------------------------------------------------------------------------
-constexpr int kRowsChunkMax = 64;     // chunks one lane group can cover: a group never spans two waves
-
-static inline bool rows_vec_ok(const void *p, int vd) { return (vd & 3) == 0 && ((uintptr_t)p & 15) == 0; }
-static inline int rows_group_shift(int nch)
-{
-    int s = 0;
-    while ((1 << s) < nch) ++s;
-    return s;
-}
-
-const char *splat_rows_launch(const int *ptr, const int *row, const float *w, const float *d_src, int vd, int m, float *d_values,
-                              hipStream_t stream)
-{
-    const int nch = values_stride(vd) / 4;
-    const bool vec = rows_vec_ok(d_src, vd);
-    float4 *v4 = reinterpret_cast<float4 *>(d_values);
-    const char *kn_rows_splat;            // (named as the member the row-range splat keeps it in)
-    if (vd == 1) {
-        kn_rows_splat = "rows_splat_v1_kernel";
-        rows_splat_v1_kernel<<<ceil_div(m, kBlock), kBlock, 0, stream>>>(ptr, row, w, d_src, m, d_values);
-    } else if (nch <= kRowsChunkMax) {
-        kn_rows_splat = "rows_splat_chunk_kernel";
-        const int shift = rows_group_shift(nch);
-        const int grid = ceil_div((int64_t)m << shift, kBlock);
-        if (vec) rows_splat_chunk_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v4);
-        else rows_splat_chunk_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, shift, m, v4);
-    } else {
-        kn_rows_splat = "rows_splat_wide_kernel";
-        const int grid = ceil_div(m, kBlock / 64);
-        if (vec) rows_splat_wide_kernel<true><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, m, v4);
-        else rows_splat_wide_kernel<false><<<grid, kBlock, 0, stream>>>(ptr, row, w, d_src, vd, nch, m, v4);
-    }
-    return kn_rows_splat;
-}
-
-int splat_rows_impl(plx_lattice *L, const float *d_src, int64_t begin, int64_t count, int vd, float *d_values,
-                           hipStream_t stream)
-{
-    plx_lattice::RowsRange *r = range_slot(L, begin, count);
-    PLX_TRY(ensure_rows_splat(L, r, stream));
-    L->kn_rows_splat = splat_rows_launch(r->ptr.as<int>(), r->row.as<int>(), r->w.as<float>(), d_src, vd, (int)L->m, d_values,
-                                         stream);
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
-}
-
-template <bool VEC>
-static void launch_slice_chunk(plx_lattice *L, const plx_lattice::RowsRange *r, const float4 *v4, int vd, int nch, float rden,
-                               float *d_out, hipStream_t stream)
-{
-    const int n = (int)L->n, d1 = L->d + 1, count = (int)r->count;
-    const int shift = rows_group_shift(nch);
-    const int grid = ceil_div((int64_t)count << shift, kBlock);
-    const int *pos = r->pos.as<int>(), *prow = r->prow.as<int>();
-    const int *evid = L->evid.as<int>();
-    const float *ew = L->ew.as<float>();
-    dispatch_d1(d1, [&](auto D1) {
-        rows_slice_chunk_kernel<VEC, decltype(D1)::value><<<grid, kBlock, 0, stream>>>(pos, prow, evid, ew, n, d1,
-                                                                                       count, v4, vd, nch, shift, rden,
-                                                                                       d_out);
-    });
-}
-
-int slice_rows_impl(plx_lattice *L, const float *d_values, int vd, int64_t begin, int64_t count, float *d_out,
-                           hipStream_t stream)
-{
-    plx_lattice::RowsRange *r = range_slot(L, begin, count);
-    PLX_TRY(ensure_rows_slice(L, r, stream));
-    const int n = (int)L->n, d1 = L->d + 1, nch = values_stride(vd) / 4;
-    const float rden = 1.0f / L->slice_denom;
-    const bool vec = rows_vec_ok(d_out, vd);
-    const float4 *v4 = reinterpret_cast<const float4 *>(d_values);
-    if (vd == 1) {
-        L->kn_rows_slice = "rows_slice_v1_kernel";
-        rows_slice_v1_kernel<<<ceil_div(count, kBlock), kBlock, 0, stream>>>(r->pos.as<int>(), r->prow.as<int>(),
-                                                                              L->evid.as<int>(), L->ew.as<float>(), n, d1,
-                                                                              (int)count, d_values, rden, d_out);
-    } else if (nch <= kRowsChunkMax) {
-        L->kn_rows_slice = "rows_slice_chunk_kernel";
-        if (vec) launch_slice_chunk<true>(L, r, v4, vd, nch, rden, d_out, stream);
-        else launch_slice_chunk<false>(L, r, v4, vd, nch, rden, d_out, stream);
-    } else {
-        L->kn_rows_slice = "rows_slice_wide_kernel";
-        const int grid = ceil_div(count, kBlock / 64);
-        if (vec)
-            rows_slice_wide_kernel<true><<<grid, kBlock, 0, stream>>>(r->pos.as<int>(), r->prow.as<int>(), L->evid.as<int>(),
-                                                                      L->ew.as<float>(), n, d1, (int)count, v4, vd, nch, rden,
-                                                                      d_out);
-        else
-            rows_slice_wide_kernel<false><<<grid, kBlock, 0, stream>>>(r->pos.as<int>(), r->prow.as<int>(), L->evid.as<int>(),
-                                                                       L->ew.as<float>(), n, d1, (int)count, v4, vd, nch, rden,
-                                                                       d_out);
-    }
-    PLX_HIP_TRY(hipGetLastError());
-    return PLX_OK;
-}
+template const char *splat_rows_launch<float>(const int *, const int *, const float *, const float *, int, int, float *, hipStream_t);
+template int splat_rows_impl<float>(plx_lattice *, const float *, int64_t, int64_t, int, float *, hipStream_t);
+template int slice_rows_impl<float>(plx_lattice *, const float *, int, int64_t, int64_t, float *, hipStream_t);
 
 }  // namespace plx

@@ -52,7 +52,7 @@ template <> struct RowsBackward<float> : RowsBackwardHost<float> {
     static constexpr const char *kContractChunk = "rows_backward_contract_chunk_kernel";
     static constexpr const char *kContractWide = "rows_backward_contract_wide_kernel";
 
-    // rows_vertex_sum over chunk ch of the half stack rows: the same weights, the same corner order, the same expression
+    // Gather<float>::vertex_sum over chunk ch of the half stack rows: the same weights, the same corner order, the same expression
     static __device__ __forceinline__ float4 half_stack_vertex_sum(const int *__restrict__ row, const float *__restrict__ w, int j0,
                                                                    int j1, const float *__restrict__ a, const float *__restrict__ x,
                                                                    int L, int d, int ch)

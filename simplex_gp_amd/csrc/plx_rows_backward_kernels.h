@@ -37,7 +37,7 @@
 //
 // What the types differ in, all of it in RowsBackward<T> (the host-side constants in RowsBackwardHost<T>, plx_internal.h):
 //   float:  float4 chunks, stride = values_stride(H) <= kBackwardRowsMaxCols = 4096.  The vertex sum is the expression of
-//           rows_vertex_sum (plx_rows.hip), acc += w[j] * element with the product element an explicit __fmul_rn.  The
+//           Gather<float>::vertex_sum (plx_kernels.h), acc += w[j] * element with the product element an explicit __fmul_rn.  The
 //           filtered chunk is rows_filtered_chunk (plx_kernels.h), which reads the point's corners itself, per chunk, and
 //           multiplies every term by the rounded reciprocal 1.0f / slice_denom: the corners type is empty.
 //   double: double2 chunks, stride = values_stride_f64(H) <= kBackwardF64MaxCols = 2048.  The vertex sum is

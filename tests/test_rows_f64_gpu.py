@@ -409,10 +409,13 @@ def test_operator_level(every_width):
 
 
 def test_every_rows_f64_family_was_reached():
-    """The literals plx_rows_f64.hip can assign to kn_rows64_splat / kn_rows64_slice are exactly the six names, and all six
-    ran above; the worst ratios against their bars per family."""
+    """The names Rows<double> (plx_rows_f64.hip) can report in kn_rows64_splat / kn_rows64_slice are exactly the six names,
+    and all six ran above; the worst ratios against their bars per family."""
     src = open(os.path.join(os.path.dirname(nv.LIB_PATH), "csrc", "plx_rows_f64.hip")).read()
-    literals = set(re.findall(r'\bkn_rows64_(?:splat|slice)\s*=\s*"([^"]*)"', src))
+    block = re.search(r"struct Rows<double>\s*\{(.*?)\n\};", src, re.S).group(1)
+    literals = set()
+    for stmt in re.finditer(r"\bk(?:Splat|Slice)(?:V1|Chunk|Wide)\s*=([^;]*);", block):
+        literals.update(re.findall(r'"([^"]*)"', stmt.group(1)))
     assert literals == set(V1 + CHUNK + WIDE), literals
     print("\nfp64 rows kernels against Lattice64: worst entry ratio / its bar k 2^-52, rel-L2 / its bar, entry ratio (cases)")
     for fam, (a, b, e, c) in sorted(WORST.items()):

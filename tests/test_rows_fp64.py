@@ -427,9 +427,12 @@ def test_prediction_on_snelson(golden_dir, every_width):
 
 
 def test_every_rows_family_was_reached():
-    """Every literal plx_rows.hip can assign to kn_rows_splat / kn_rows_slice ran above; the worst bars per family."""
+    """Every name Rows<float> (plx_rows.hip) can report in kn_rows_splat / kn_rows_slice ran above; the worst bars per family."""
     src = open(os.path.join(os.path.dirname(nv.LIB_PATH), "csrc", "plx_rows.hip")).read()
-    literals = set(re.findall(r'\bkn_rows_(?:splat|slice)\s*=\s*"([^"]*)"', src))
+    block = re.search(r"struct Rows<float>\s*\{(.*?)\n\};", src, re.S).group(1)
+    literals = set()
+    for stmt in re.finditer(r"\bk(?:Splat|Slice)(?:V1|Chunk|Wide)\s*=([^;]*);", block):
+        literals.update(re.findall(r'"([^"]*)"', stmt.group(1)))
     assert literals == set(V1 + CHUNK + WIDE), literals
     print("\nrows kernels against float64: worst entry ratio / rel-L2 per family (cases)")
     for fam, (e, r, c) in sorted(WORST.items()):
